@@ -7,6 +7,19 @@ nx = ny = nz = 200 problem per GPU (BASELINE.json configs[2]), matrix, b and
 x resident in HBM before the timed region (device generator).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--n 200] [--stencil 27]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: set up, W warmup steps,
+the K timed steps, the line. `value`, `ms_per_step`, `roofline` and
+`check` (without trace_vs_oracle) come from those steps alone. --full adds,
+after the timed steps, everything else described below: cpu_baseline,
+check.trace_vs_oracle, secondary and host_boundary (each still switched off by
+its own --no-* option); without --full they are absent (cpu_baseline null).
+--dump-outputs DIR writes what the last timed solve returned to its caller as
+DIR/<name>.npy (float64): x (every entry, or a fixed seeded sample of
+DUMP_MAX_X entries of a larger x), niters, normr and the residual trace; N > 1:
+<name>_rank<r>.npy per rank. The problem is generated without an RNG, so the
+same arguments give the same inputs in every run.
 
 N > 1: one process per rank under torch.distributed.run (the driver's launch;
 `python bench.py --gpus N` without WORLD_SIZE starts that launcher itself as a
@@ -19,7 +32,7 @@ ranks share GPUs and bootstrap through the host (hpccg_hip_comm_init_host),
 running the same in-kernel transport between processes. torch.distributed
 (gloo) carries only the control plane (unique id / setup all-gathers, barrier,
 max-over-ranks time). The line carries every rank's transport verdicts, the
-max-over-ranks SpMV launch time, and a CPU leg on the global problem.
+max-over-ranks SpMV launch time, and (--full) a CPU leg on the global problem.
 
 value = (CG iterations x ranks x K) / max-over-ranks wall time of the K steps
       = 200^3-slab CG iterations per second summed over GPUs.
@@ -35,6 +48,7 @@ roofline (the SpMV kernel, 84 % of the reference's time):
   (profiles/pmc_spmv_<stencil>pt_<n>.json), or null. credited_frac keeps
   SURVEY 8(d)'s fixed formula (12 nnz + 20 n SpMV + ddot/waxpby bytes the
   fused kernel absorbs) is reported as bytes only.
+The rest is measured only with --full.
 cpu_baseline: the reference compiled from its own sources (oracle/_ref) on
   a bounded sample of the same problem, run by rank 0 after every GPU step in
   a fresh child process (`bench.py --cpu-child`) whose CPU mask is widened to
@@ -94,6 +108,8 @@ RTRANS_CUTOFF = 1e-20
 TRACE_MIN_POINTS = 5
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 COPY_CEILING_GBS = 6290.0  # MI355X_MICROARCH.md: float4 copy, measured
+DUMP_MAX_X = 1 << 22   # --dump-outputs: entries of x written (32 MB of float64), over all ranks
+DUMP_SEED = 20240607   # ... and the seed of the sample taken from a larger x
 KERNEL_NAMES = {0: "k_spmv_sell", 1: "k_spmv_a", 2: "k_spmv_a2", 3: "k_spmv_a2r", 4: "k_spmv_ar", 5: "k_cg_persist"}
 FORMAT_NAMES = {0: "SELL-512 (8 B value + 4 B int32 column per slot)",
                 1: "SELL-512-A (8 B value per offset-aligned slot, holes 0.0), x read at the slice's offsets",
@@ -581,7 +597,26 @@ def measure(hp, torch, M, dev, max_iter, steps, warmup, event_steps, world, dist
             "spmv_avg_s": spmv_avg_s, "timing_src": timing_src, "upd_ms": upd_ms, "upd_n": upd_n,
             "times_acc": times_acc, "step_s": step_s, "cold_s": cold_s, "graph_used": graph_used,
             "chk": [chk[0].item(), chk[1].item(), int(chk[2].item())], "steps": steps, "event_steps": event_steps,
-            "trace": [float(v) for v in tr]}
+            "trace": [float(v) for v in tr], "x": x, "normr": float(nr)}
+
+
+def dump_outputs(dirpath, meas, rank, world):
+    """--dump-outputs: what the last timed solve handed its caller (x in place,
+    niters, normr) and its residual trace, as float64 .npy files. An x of more
+    than DUMP_MAX_X entries over the ranks is sampled at fixed, seeded rows."""
+    import numpy as np
+    import torch
+    os.makedirs(dirpath, exist_ok=True)
+    x = meas["x"]
+    n, cap = x.numel(), max(1, DUMP_MAX_X // world)
+    if n > cap:
+        rows = np.sort(np.random.RandomState(DUMP_SEED).choice(n, cap, replace=False))
+        xs = x[torch.from_numpy(rows).to(x.device)].cpu().numpy()
+    else:
+        xs = x.cpu().numpy()
+    sfx = "" if world == 1 else f"_rank{rank}"
+    for name, a in (("x", xs), ("niters", [meas["it"]]), ("normr", [meas["normr"]]), ("trace", meas["trace"])):
+        np.save(os.path.join(dirpath, f"{name}{sfx}.npy"), np.asarray(a, dtype=np.float64))
 
 
 def roofline_of(M, n, stencil, spmv_avg_s):
@@ -799,6 +834,7 @@ def build_line(args, world, n, meas, roof, kernel, kfmt, fused, info, M_opts, rt
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": bool(getattr(args, "full", False)),
         "ms_per_step": round(meas["elapsed"] / args.steps * 1e3, 3),
         "higher_is_better": True,
         "scaling": "weak",
@@ -866,6 +902,12 @@ def main():
     ap.add_argument("--n", type=int, default=200, help="nx = ny = nz per GPU")
     ap.add_argument("--stencil", type=int, default=27, choices=[27, 7])
     ap.add_argument("--max-iter", type=int, default=500)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure cpu_baseline, check.trace_vs_oracle, secondary and "
+                         "host_boundary (the --no-* options below switch single ones off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed solve's x (sampled when large), niters, normr and residual trace "
+                         "to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-host-boundary", action="store_true",
                     help="N = 1: skip the host-interface rate (hpccg_hip_HPCCG with host b and x)")
@@ -899,6 +941,8 @@ def main():
                     help="timed steps launched eagerly with hipEvents around every SpMV (the roofline's kernel "
                          "time); the other timed steps replay hipGraphs")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the timed steps and their line only
+        args.no_cpu_baseline = args.no_host_boundary = args.no_secondary = args.no_trace_check = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -963,6 +1007,10 @@ def main():
 
     meas = measure(hp, torch, M, dev, args.max_iter, args.steps, args.warmup, args.event_steps, world, dist, stage)
     stage("timed", steps=args.steps, seconds=f"{meas['elapsed']:.3f}")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, meas, rank, world)
+        stage("dump_outputs", dir=args.dump_outputs)
+    del meas["x"]
     roof, kernel, kfmt, fused, fupd = roofline_of(M, n, args.stencil, meas["spmv_avg_s"])
     M_opts = {k: opt_or_none(M, k) for k in ("fuse_p", "fold", "x_defer", "x_ring", "graph_chunk", "nt", "a2_ring",
                                              "nt_store", "fuse_update", "rhalo", "peer_allreduce", "halo_pull",
@@ -1025,9 +1073,11 @@ def main():
             for i, (n2, st2, _) in sec_traces.items():
                 spec["traces"][f"secondary{i}"] = {"nx": n2, "ny": n2, "nz": n2 * world, "use_7pt": st2 == 7,
                                                    "iters": args.trace_iters, "budget_s": 10.0}
-        stage("cpu_child_run", baseline=bool(spec.get("baseline")), traces=len(spec["traces"]))
-        child = run_cpu_child(spec, 900.0) if (spec.get("baseline") or spec["traces"]) else {}
-        stage("cpu_child", seconds=child.get("seconds"), error=child.get("error"))
+        child = {}
+        if spec.get("baseline") or spec["traces"]:
+            stage("cpu_child_run", baseline=bool(spec.get("baseline")), traces=len(spec["traces"]))
+            child = run_cpu_child(spec, 900.0)
+            stage("cpu_child", seconds=child.get("seconds"), error=child.get("error"))
         cpu = None
         if not args.no_cpu_baseline:
             cpu = child.get("baseline") or {"error": child.get("error", "no baseline from the cpu child")}

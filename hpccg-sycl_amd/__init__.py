@@ -143,6 +143,54 @@ def lib() -> C.CDLL:
     return L
 
 
+BATCH_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_batch.so")
+_batch_lib = None
+
+
+def batch_lib() -> C.CDLL:
+    """Load libhpccg_hip_batch.so (include/hpccg_hip_batch.h) on first use. It
+    is linked against libhpccg_hip.so beside it, so lib() is loaded first and
+    both share one copy of the main library."""
+    global _batch_lib
+    if _batch_lib is not None:
+        return _batch_lib
+    if os.environ.get("HPCCG_HIP_LIB", LIB_PATH) != LIB_PATH:
+        raise HPCCGError("the batch library runs on the in-tree libhpccg_hip.so only (HPCCG_HIP_LIB is set)")
+    lib()
+    if not os.path.exists(BATCH_LIB_PATH):
+        raise HPCCGError(f"{BATCH_LIB_PATH} missing: run build() (the batched solve has no fallback)")
+    try:
+        L = C.CDLL(BATCH_LIB_PATH)
+    except OSError as e:
+        raise HPCCGError(f"{BATCH_LIB_PATH} does not load: {e}") from e
+    vp, ip, dp, lp = C.c_void_p, C.c_int, C.c_double, C.c_longlong
+    PI, PD = C.POINTER(C.c_int), C.POINTER(C.c_double)
+    sig = {
+        "hpccg_hip_batch_abi_version": (ip, []),
+        "hpccg_hip_batch_solve_device": (ip, [vp, ip, vp, lp, vp, lp, ip, dp, PI, PD, PD]),
+        "hpccg_hip_batch_solve": (ip, [vp, ip, vp, lp, vp, lp, ip, dp, PI, PD, PD]),
+        "hpccg_hip_batch_last_trace": (ip, [vp, ip, PD, ip]),
+        "hpccg_hip_batch_sparsemv": (ip, [vp, ip, vp, lp, vp, lp]),
+        "hpccg_hip_batch_release": (ip, [vp]),
+        "hpccg_hip_batch_workspace_bytes": (ip, [vp, C.POINTER(lp)]),
+        "hpccg_hip_batch_live_workspaces": (ip, [PI]),
+    }
+    for name, (res, args) in sig.items():
+        f = getattr(L, name)
+        f.restype = res
+        f.argtypes = args
+    _batch_lib = L
+    return L
+
+
+def batch_exported_symbols() -> list[str]:
+    """Functions include/hpccg_hip_batch.h declares (checked by the CPU suite)."""
+    import re
+    with open(os.path.join(ROOT, "include", "hpccg_hip_batch.h")) as f:
+        text = f.read()
+    return sorted(set(re.findall(r"\b(hpccg_hip_batch_\w+)\s*\(", text)))
+
+
 def exported_symbols() -> list[str]:
     """Functions include/hpccg_hip.h declares (checked by the CPU suite)."""
     import re
@@ -387,7 +435,29 @@ class Matrix:
         n = lib().hpccg_hip_last_trace(self.h, out.ctypes.data_as(C.POINTER(C.c_double)), cap)
         return out[:max(n, 0)]
 
+    def last_trace_batch(self, col: int, cap: int = 100000) -> np.ndarray:
+        """Residual trace of column col of the last HPCCG_batch on this matrix."""
+        out = np.zeros(cap, np.float64)
+        n = batch_lib().hpccg_hip_batch_last_trace(self.h, int(col), out.ctypes.data_as(C.POINTER(C.c_double)), cap)
+        if n < 0:
+            _check(n, "last_trace_batch")
+        return out[:n]
+
+    def batch_release(self) -> None:
+        """Free this matrix's batch workspace now (close() does it too)."""
+        if self.h and _batch_lib is not None:
+            _check(_batch_lib.hpccg_hip_batch_release(self.h), "batch_release")
+
+    def batch_workspace_bytes(self) -> int:
+        if _batch_lib is None:
+            return 0
+        v = C.c_longlong(0)
+        _check(_batch_lib.hpccg_hip_batch_workspace_bytes(self.h, C.byref(v)), "batch_workspace_bytes")
+        return v.value
+
     def close(self):
+        # (a batch workspace goes with the matrix: the library's destroy hook,
+        # whether or not the batch library was ever loaded)
         if self.h:
             lib().hpccg_hip_matrix_destroy(self.h)
             self.h = None
@@ -433,6 +503,73 @@ def HPCCG(M: Matrix, b, x, max_iter: int = 500, tolerance: float = 0.0, print_re
                                C.byref(it), C.byref(nr), tp, int(print_residuals))
     _check(rc, "HPCCG")
     return rc, it.value, nr.value, times
+
+
+# ---------------------------------------------------------------------------
+# batched multi-right-hand-side solve (include/hpccg_hip_batch.h)
+# ---------------------------------------------------------------------------
+def _cols(a, nrhs, ld, what):
+    """(pointer, nrhs, ld) of a column set: a 2-D array whose row c is column c
+    (numpy C-contiguous float64, or a torch tensor with unit inner stride; the
+    row stride is the leading dimension), or a raw pointer with nrhs and ld."""
+    if isinstance(a, int):
+        if nrhs is None or ld is None:
+            raise HPCCGError(f"{what}: a raw pointer needs nrhs and its leading dimension")
+        return a, int(nrhs), int(ld)
+    if isinstance(a, np.ndarray):
+        if a.dtype != np.float64 or a.ndim != 2 or not a.flags.c_contiguous:
+            raise HPCCGError(f"{what}: a C-contiguous float64 array of shape (nrhs, ld)")
+        return a.ctypes.data, a.shape[0], a.shape[1] if ld is None else int(ld)
+    if a.dim() != 2 or (a.shape[1] > 1 and a.stride(1) != 1):
+        raise HPCCGError(f"{what}: a 2-D tensor of shape (nrhs, ld) with unit inner stride")
+    if ld is None:
+        ld = a.stride(0) if a.shape[0] > 1 else a.shape[1]
+    return _ptr(a), a.shape[0], int(ld)
+
+
+def HPCCG_batch(M: Matrix, B, X, max_iter: int = 500, tolerance: float = 0.0, device=False, nrhs=None,
+                ldb=None, ldx=None):
+    """nrhs CG solves against M in one pass over the matrix per iteration
+    (hpccg_hip_batch_solve[_device]); column c is bitwise HPCCG(M, B[c], X[c]).
+    B, X: shape (nrhs, ld) with row c holding column c (ld >= nrow; the C
+    ABI's column-major layout) -- numpy on the host or, with device=True,
+    tensors / device pointers. X is updated in place. Returns
+    (ierr, niters[nrhs], normr[nrhs], times)."""
+    L = batch_lib()
+    bp, nb, ldb_ = _cols(B, nrhs, ldb, "B")
+    xp, nx_, ldx_ = _cols(X, nrhs, ldx, "X")
+    if nb != nx_:
+        raise HPCCGError(f"B holds {nb} columns, X {nx_}")
+    if not device and not (isinstance(B, np.ndarray) and isinstance(X, np.ndarray)):
+        raise HPCCGError("host solve: B and X are numpy arrays")
+    it = np.zeros(max(nb, 1), np.int32)
+    nr = np.zeros(max(nb, 1), np.float64)
+    times = np.zeros(7, np.float64)
+    f = L.hpccg_hip_batch_solve_device if device else L.hpccg_hip_batch_solve
+    rc = f(M.h, nb, bp, ldb_, xp, ldx_, max_iter, tolerance, it.ctypes.data_as(C.POINTER(C.c_int)),
+           nr.ctypes.data_as(C.POINTER(C.c_double)), times.ctypes.data_as(C.POINTER(C.c_double)))
+    _check(rc, "HPCCG_batch")
+    return rc, it[:nb], nr[:nb], times
+
+
+def HPC_sparsemv_batch(M: Matrix, X, Y, nrhs=None, ldx=None, ldy=None) -> int:
+    """Y[c] = A X[c] for every column (device tensors / pointers, shape
+    (nrhs, ld)); each column is bitwise HPC_sparsemv of that column."""
+    xp, nx_, ldx_ = _cols(X, nrhs, ldx, "X")
+    yp, ny_, ldy_ = _cols(Y, nrhs, ldy, "Y")
+    if nx_ != ny_:
+        raise HPCCGError(f"X holds {nx_} columns, Y {ny_}")
+    _check(batch_lib().hpccg_hip_batch_sparsemv(M.h, nx_, xp, ldx_, yp, ldy_), "HPC_sparsemv_batch")
+    return 0
+
+
+def batch_live_workspaces() -> int:
+    """Matrices that hold a batch workspace (0 when the library was never loaded)."""
+    if _batch_lib is None:
+        return 0
+    c = C.c_int(0)
+    _check(_batch_lib.hpccg_hip_batch_live_workspaces(C.byref(c)), "batch_live_workspaces")
+    return c.value
 
 
 # ---------------------------------------------------------------------------

@@ -319,4 +319,45 @@ void launch_a_offsets(const unsigned int* slice_base, int nslices, const int* co
 void launch_a_fill(const unsigned int* slice_base, int nslices, const int* cols, const double* vals, int ghost_lo,
                    const int* aoff, const int* acount, const unsigned int* abase, double* aval, hipStream_t s);
 
+// Read-only view of a device matrix for the batch library (libhpccg_hip_batch.so,
+// csrc/hpccg_batch.hip): what its kernels need of the matrix images and of the
+// single solve's vector layout. The pointers belong to the matrix and stay
+// valid until it is destroyed (the destroy hook below tells the holder).
+struct MatrixView {
+    int device;
+    int n;                 // local rows
+    int nslices;           // ceil(n / kSliceRows)
+    int grid;              // nslices rounded up to a multiple of kNumXcd
+    long long npad;        // rows of every padded vector (a multiple of kSliceRows)
+    int nranks;            // z-slab ranks of the matrix's communicator or group
+    int in_group;          // 1: a member of an in-process group
+    int ghost_lo, ghost_hi;  // halo rows below / above
+    // SELL-512-A (has_a): values in per-slice offset-aligned slots
+    int has_a;
+    int a_width;           // uniform slot count (27, 7, ...), 0 = per-slice widths
+    int nt;                // the single solve streams the values non-temporally
+    const double* aval;
+    const int* aoff;              // per slice, kAMax offsets
+    const unsigned int* abase;    // [nslices + 1] first slot row of each slice
+    // SELL-512 (has_sell): kept only when no A image exists (or on request)
+    int has_sell;
+    const unsigned int* slice_base;
+    const int* cols;
+    const double* vals;
+    long long guard_rows;  // kGuardRows: the zeroed zone on each side of p and r
+    long long pstride;     // distance between the single solve's p buffers (doubles)
+    hipStream_t stream;    // the matrix's stream
+};
+
 }  // namespace hpccg
+
+struct hpccg_hip_matrix;
+extern "C" {
+// Internal seams for the batch library; not declared in include/hpccg_hip.h.
+int hpccg_hip_internal_view(const hpccg_hip_matrix* M, hpccg::MatrixView* out);
+// fn(ctx) runs at the start of hpccg_hip_matrix_destroy(M) (the matrix still
+// whole, its device current), once; registering the same (fn, ctx) twice is one hook.
+int hpccg_hip_internal_on_destroy(hpccg_hip_matrix* M, void (*fn)(void*), void* ctx);
+// the calling thread's hpccg_hip_last_error() message; returns code
+int hpccg_hip_internal_set_error(int code, const char* msg);
+}

@@ -411,6 +411,8 @@ struct hpccg_hip_matrix {
     std::vector<double> kiter;  // event_timing: per iteration {SpMV ms, update ms}
     std::vector<double> trace;
     int last_niters = 0;
+    // hpccg_hip_internal_on_destroy: run at the start of hpccg_hip_matrix_destroy
+    std::vector<std::pair<void (*)(void*), void*>> destroy_hooks;
 };
 
 namespace {
@@ -601,6 +603,14 @@ void dev_free(hpccg_hip_matrix* M, T** p, size_t count)
 int free_matrix(hpccg_hip_matrix* M)
 {
     if (!M) return 0;
+    // holders of workspaces keyed by M (hpccg_hip_internal_on_destroy: the
+    // batch library) let go first, while the matrix is still whole
+    if (!M->destroy_hooks.empty()) {
+        const auto hooks = std::move(M->destroy_hooks);
+        M->destroy_hooks.clear();
+        (void)hipSetDevice(M->device);
+        for (const auto& h : hooks) h.first(h.second);
+    }
     // Nothing may write into this matrix's memory once it is freed and reused:
     // its own streams, and in a group the other members' kernels, which store
     // into its mailbox (peer all-reduce) or read its planes -- every device of
@@ -3822,6 +3832,51 @@ int hpccg_hip_set_placement_probe(int tries)
 }
 
 int hpccg_hip_matrix_destroy(hpccg_hip_matrix* M) { return free_matrix(M); }
+
+// ---------------------------------------------------------------------------
+// internal seams for libhpccg_hip_batch.so (hpccg_internal.h)
+// ---------------------------------------------------------------------------
+int hpccg_hip_internal_view(const hpccg_hip_matrix* M, MatrixView* out)
+{
+    if (!M || !out) return set_err(HPCCG_HIP_EINVAL, "NULL argument");
+    MatrixView v;
+    std::memset(&v, 0, sizeof v);
+    v.device = M->device;
+    v.n = M->nrow;
+    v.nslices = M->nslices;
+    v.grid = M->grid;
+    v.npad = (long long)M->npad;
+    v.nranks = M->nranks;
+    v.in_group = M->in_group;
+    v.ghost_lo = M->ghost_lo;
+    v.ghost_hi = M->ghost_hi;
+    v.has_a = M->has_a;
+    v.a_width = M->a_width;
+    v.nt = nt_load_of(M) ? 1 : 0;
+    v.aval = M->d_aval;
+    v.aoff = M->d_aoff;
+    v.abase = M->d_abase;
+    v.has_sell = M->has_sell;
+    v.slice_base = M->d_slice_base;
+    v.cols = M->d_cols;
+    v.vals = M->d_vals;
+    v.guard_rows = kGuardRows;
+    v.pstride = M->pstride;
+    v.stream = M->stream;
+    *out = v;
+    return 0;
+}
+
+int hpccg_hip_internal_on_destroy(hpccg_hip_matrix* M, void (*fn)(void*), void* ctx)
+{
+    if (!M || !fn) return set_err(HPCCG_HIP_EINVAL, "NULL argument");
+    for (const auto& h : M->destroy_hooks)
+        if (h.first == fn && h.second == ctx) return 0;
+    M->destroy_hooks.emplace_back(fn, ctx);
+    return 0;
+}
+
+int hpccg_hip_internal_set_error(int code, const char* msg) { return set_err(code, "%s", msg ? msg : ""); }
 
 int hpccg_hip_matrix_info(const hpccg_hip_matrix* M, long long info[8])
 {

@@ -174,6 +174,13 @@ def batch_lib() -> C.CDLL:
         "hpccg_hip_batch_release": (ip, [vp]),
         "hpccg_hip_batch_workspace_bytes": (ip, [vp, C.POINTER(lp)]),
         "hpccg_hip_batch_live_workspaces": (ip, [PI]),
+        # include/hpccg_hip_batch_group.h
+        "hpccg_hip_group_batch_abi_version": (ip, []),
+        "hpccg_hip_group_batch_solve_device": (ip, [C.POINTER(vp), ip, ip, C.POINTER(vp), C.POINTER(lp),
+                                                    C.POINTER(vp), C.POINTER(lp), ip, dp, PI, PD, PD]),
+        "hpccg_hip_group_batch_sparsemv": (ip, [C.POINTER(vp), ip, ip, C.POINTER(vp), C.POINTER(lp),
+                                                C.POINTER(vp), C.POINTER(lp)]),
+        "hpccg_hip_group_batch_last_trace": (ip, [C.POINTER(vp), ip, ip, PD, ip]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -189,6 +196,14 @@ def batch_exported_symbols() -> list[str]:
     with open(os.path.join(ROOT, "include", "hpccg_hip_batch.h")) as f:
         text = f.read()
     return sorted(set(re.findall(r"\b(hpccg_hip_batch_\w+)\s*\(", text)))
+
+
+def group_batch_exported_symbols() -> list[str]:
+    """Functions include/hpccg_hip_batch_group.h declares (checked by the CPU suite)."""
+    import re
+    with open(os.path.join(ROOT, "include", "hpccg_hip_batch_group.h")) as f:
+        text = f.read()
+    return sorted(set(re.findall(r"\b(hpccg_hip_group_batch_\w+)\s*\(", text)))
 
 
 def exported_symbols() -> list[str]:
@@ -621,6 +636,79 @@ def group_HPCCG(Ms: list, bs, xs, max_iter: int = 500, tolerance: float = 0.0):
                                      times.ctypes.data_as(C.POINTER(C.c_double)))
     _check(rc, "group_HPCCG")
     return rc, it.value, nr.value, times
+
+
+# ---------------------------------------------------------------------------
+# batched solve over an in-process group (include/hpccg_hip_batch_group.h)
+# ---------------------------------------------------------------------------
+def _group_cols(As, nrhs, lds, what):
+    """Per member (pointer, nrhs, ld) of its column set (see _cols); lds: one
+    leading dimension for all, one per member, or None."""
+    P = len(As)
+    if lds is None or isinstance(lds, int):
+        lds = [lds] * P
+    got = [_cols(a, nrhs, ld, f"{what}[{r}]") for r, (a, ld) in enumerate(zip(As, lds))]
+    if len({g[1] for g in got}) > 1:
+        raise HPCCGError(f"{what}: the members hold different numbers of columns {[g[1] for g in got]}")
+    ptrs = (C.c_void_p * P)(*[g[0] for g in got])
+    ld = (C.c_longlong * P)(*[g[2] for g in got])
+    return ptrs, (got[0][1] if got else 0), ld
+
+
+def group_HPCCG_batch(Ms: list, Bs, Xs, max_iter: int = 500, tolerance: float = 0.0, nrhs=None, ldb=None,
+                      ldx=None):
+    """nrhs CG solves over an in-process group in one pass over the matrix per
+    iteration (hpccg_hip_group_batch_solve_device); column c is bitwise
+    group_HPCCG of that column alone. Bs[r], Xs[r]: member r's rows of every
+    column on its device, shape (nrhs, ld) with row c holding column c
+    (ld >= the member's nrow) -- tensors, or device pointers with nrhs and the
+    leading dimensions. Xs is updated in place. Returns
+    (niters[nrhs], normr[nrhs], times)."""
+    L = batch_lib()
+    P = len(Ms)
+    if len(Bs) != P or len(Xs) != P:
+        raise HPCCGError(f"{P} members, {len(Bs)} B and {len(Xs)} X column sets")
+    hs = (C.c_void_p * P)(*[M.h for M in Ms])
+    bp, nb, ldb_ = _group_cols(Bs, nrhs, ldb, "Bs")
+    xp, nx_, ldx_ = _group_cols(Xs, nrhs, ldx, "Xs")
+    if nb != nx_:
+        raise HPCCGError(f"Bs holds {nb} columns, Xs {nx_}")
+    it = np.zeros(max(nb, 1), np.int32)
+    nr = np.zeros(max(nb, 1), np.float64)
+    times = np.zeros(7, np.float64)
+    rc = L.hpccg_hip_group_batch_solve_device(hs, P, nb, bp, ldb_, xp, ldx_, max_iter, tolerance,
+                                              it.ctypes.data_as(C.POINTER(C.c_int)),
+                                              nr.ctypes.data_as(C.POINTER(C.c_double)),
+                                              times.ctypes.data_as(C.POINTER(C.c_double)))
+    _check(rc, "group_HPCCG_batch")
+    return it[:nb], nr[:nb], times
+
+
+def group_sparsemv_batch(Ms: list, Xs, Ys, nrhs=None, ldx=None, ldy=None) -> int:
+    """Ys[r][c] = member r's rows of A Xs[:][c] for every column (the global
+    matrix; the halo of X is exchanged inside)."""
+    P = len(Ms)
+    if len(Xs) != P or len(Ys) != P:
+        raise HPCCGError(f"{P} members, {len(Xs)} X and {len(Ys)} Y column sets")
+    hs = (C.c_void_p * P)(*[M.h for M in Ms])
+    xp, nx_, ldx_ = _group_cols(Xs, nrhs, ldx, "Xs")
+    yp, ny_, ldy_ = _group_cols(Ys, nrhs, ldy, "Ys")
+    if nx_ != ny_:
+        raise HPCCGError(f"Xs holds {nx_} columns, Ys {ny_}")
+    _check(batch_lib().hpccg_hip_group_batch_sparsemv(hs, P, nx_, xp, ldx_, yp, ldy_), "group_sparsemv_batch")
+    return 0
+
+
+def group_last_trace_batch(Ms: list, col: int, cap: int = 100000) -> np.ndarray:
+    """Residual trace of column col of the last group_HPCCG_batch on Ms."""
+    P = len(Ms)
+    hs = (C.c_void_p * P)(*[M.h for M in Ms])
+    out = np.zeros(cap, np.float64)
+    n = batch_lib().hpccg_hip_group_batch_last_trace(hs, P, int(col), out.ctypes.data_as(C.POINTER(C.c_double)),
+                                                     cap)
+    if n < 0:
+        _check(n, "group_last_trace_batch")
+    return out[:n]
 
 
 def HPC_sparsemv(M: Matrix, x, y) -> int:

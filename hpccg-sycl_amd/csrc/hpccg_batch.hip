@@ -21,6 +21,13 @@
 // ended) and stops launching when all have. A column that has ended is frozen:
 // its blocks skip its loads and stores (block-uniform branches). No kernel here
 // waits on another block.
+//
+// Over an in-process rank group (include/hpccg_hip_batch_group.h; the last part
+// of the host code): every member runs these kernels on its rows, the ghost
+// planes of every column's p are copied between the members' p columns after
+// k_batch_p, k_batch_finalize stores each member's local total only (local),
+// and k_batch_group_sum adds the totals in rank order and advances the column's
+// state on every member. Column c is bitwise hpccg_hip_group_solve of it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,6 +42,7 @@
 #include <vector>
 
 #include "../../include/hpccg_hip_batch.h"
+#include "../../include/hpccg_hip_batch_group.h"
 #include "hpccg_device.h"
 #include "hpccg_internal.h"
 
@@ -44,7 +52,8 @@ namespace hpccg {
 
 namespace {
 
-// Per-column scalar state, advanced by k_batch_finalize only.
+// Per-column scalar state, advanced by k_batch_finalize only (a group member's:
+// by k_batch_group_sum only).
 struct ColState {
     double rtrans;     // r_{k-1}.r_{k-1} of the iteration k about to run (HPCCG.cpp: rtrans)
     double oldrtrans;  // r_{k-2}.r_{k-2}
@@ -70,7 +79,10 @@ struct BatchArgs {
     int force;     // 1: every column runs whatever its state (the plain SpMM)
     int nt, a_width;
     int tri;       // width 27: slices whose offsets come in runs of three use the x-triple plan
-    double* p;    // local row 0 of column 0; column c at p + c * pcs (guard zones around each)
+    double* p;    // local row 0 of column 0; column c at p + c * pcs (guard zones around each;
+                  // a group member: ghost_lo rows below row 0, ghost_hi rows from row n)
+    long long xsell;  // SELL-512 column 0 relative to local row 0 (a group member: -ghost_lo)
+    double* tot;      // [2][cap] a group member's local dot totals (k_batch_finalize, local)
     double* r;
     double* Ap;    // column c at Ap + c * vcs
     double* x;
@@ -329,7 +341,7 @@ __global__ __launch_bounds__(kBlock) void k_batch_spmm_sell(BatchArgs a, bool pr
     const int w = (int)(sld(a.slice_base + s + 1) - sld(a.slice_base + s));
     const double* __restrict__ vp = a.vals + base;
     const int* __restrict__ cp = a.cols + base;
-    const double* __restrict__ x0 = a.p + (size_t)a.c0 * a.pcs;
+    const double* __restrict__ x0 = a.p + ((long long)a.c0 * a.pcs + a.xsell);
     double sum[kR][kRpt];
 #pragma unroll
     for (int c = 0; c < kR; c++)
@@ -416,7 +428,33 @@ __global__ __launch_bounds__(kBlock) void k_batch_update(BatchArgs a, bool prolo
 constexpr int kFinThreads = 1024;
 constexpr int kFinLds = 2048;  // group sums kept in LDS up to 128 K slices
 
-__global__ __launch_bounds__(kFinThreads) void k_batch_finalize(BatchArgs a, int which)
+// The column's scalars once a dot's total is known (one lane).
+__device__ __forceinline__ void advance_column(const BatchArgs& a, ColState* st, int c, int which, double tot)
+{
+    if (which == kDotPAP) {
+        st->pap = tot;
+        st->alpha = st->rtrans / tot;
+        return;
+    }
+    const int k = st->k;
+    const double old = st->rtrans;  // r_{k-1}.r_{k-1} (k >= 1)
+    a.hist[(size_t)c * a.hstride + k] = tot;
+    st->oldrtrans = old;
+    st->rtrans = tot;
+    st->beta = (k == 0) ? 0.0 : tot / old;
+    st->k = k + 1;
+    const bool run = k + 1 < a.max_iter && sqrt(k == 0 ? tot : old) > a.tol;
+    if (!run) {
+        st->run = 0;
+        st->niters = k;
+        atomicAdd(a.ended, 1);
+    }
+}
+
+// local (a member of an in-process group): the total is this member's part of
+// the dot; it is stored in tot[which][c] and the state is left to
+// k_batch_group_sum.
+__global__ __launch_bounds__(kFinThreads) void k_batch_finalize(BatchArgs a, int which, int local)
 {
     __shared__ double gs[kFinLds];
     const int c = blockIdx.x;
@@ -455,24 +493,40 @@ __global__ __launch_bounds__(kFinThreads) void k_batch_finalize(BatchArgs a, int
     const double tot = in_lds ? top_sum_wave([&](int i) { return gs[i]; }, ng, lane)
                               : top_sum_wave([gp](int i) { return gp[i]; }, ng, lane);
     if (lane != 0) return;
-    if (which == kDotPAP) {
-        st->pap = tot;
-        st->alpha = st->rtrans / tot;
+    if (local) {
+        a.tot[(size_t)which * a.cap + c] = tot;
         return;
     }
-    const int k = st->k;
-    const double old = st->rtrans;  // r_{k-1}.r_{k-1} (k >= 1)
-    a.hist[(size_t)c * a.hstride + k] = tot;
-    st->oldrtrans = old;
-    st->rtrans = tot;
-    st->beta = (k == 0) ? 0.0 : tot / old;
-    st->k = k + 1;
-    const bool run = k + 1 < a.max_iter && sqrt(k == 0 ? tot : old) > a.tol;
-    if (!run) {
-        st->run = 0;
-        st->niters = k;
-        atomicAdd(a.ended, 1);
-    }
+    advance_column(a, st, c, which, tot);
+}
+
+// ---------------------------------------------------------------------------
+// In-process group: one thread per column on member 0's stream, after every
+// member's local finalize. The global dot is the members' local totals added
+// in rank order from 0.0 (k_group_sum's sum in hpccg_kernels.hip); the column's
+// state advances as in k_batch_finalize and is stored into every member's
+// state array (peer pointers across devices), so all members freeze a column
+// together. hist and the "columns ended" word are member 0's (a: its args).
+// ---------------------------------------------------------------------------
+constexpr int kMaxMembers = kMaxGroupRanks;
+
+struct GroupTotals {
+    int nranks;
+    int cap[kMaxMembers];            // stride of member r's totals
+    const double* tot[kMaxMembers];  // member r's [2][cap] local totals
+    ColState* st[kMaxMembers];       // member r's column states
+};
+
+__global__ void k_batch_group_sum(BatchArgs a, GroupTotals g, int which)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.nrhs) return;
+    ColState s = a.st[c];
+    if (!s.run) return;  // frozen on every member
+    double v = 0.0;
+    for (int r = 0; r < g.nranks; r++) v += g.tot[r][(size_t)which * g.cap[r] + c];
+    advance_column(a, &s, c, which, v);
+    for (int r = 0; r < g.nranks; r++) g.st[r][c] = s;
 }
 
 // ---------------------------------------------------------------------------
@@ -510,6 +564,9 @@ struct Workspace {
     long long pcs = 0, vcs = 0;
     double *pbuf = nullptr, *rbuf = nullptr, *Ap = nullptr, *x = nullptr, *b = nullptr;
     double *partial = nullptr, *gsum = nullptr;
+    long long p0 = 0;       // local row 0 inside a p / r column (guard zone + the padded ghost_lo rows)
+    double* tot = nullptr;  // [2][cap] local dot totals (a group member)
+    hipEvent_t evr = nullptr, evs = nullptr;  // group: this member's stream is ready | member 0: the sum is done
     ColState* st = nullptr;
     int* ended = nullptr;
     double* hist = nullptr;
@@ -527,9 +584,9 @@ void free_device(Workspace* w)
 {
     if (w->v.stream) (void)hipStreamSynchronize(w->v.stream);
     for (void* q : {(void*)w->pbuf, (void*)w->rbuf, (void*)w->Ap, (void*)w->x, (void*)w->b, (void*)w->partial,
-                    (void*)w->gsum, (void*)w->st, (void*)w->ended, (void*)w->hist})
+                    (void*)w->gsum, (void*)w->st, (void*)w->ended, (void*)w->hist, (void*)w->tot})
         if (q) (void)hipFree(q);
-    w->pbuf = w->rbuf = w->Ap = w->x = w->b = w->partial = w->gsum = w->hist = nullptr;
+    w->pbuf = w->rbuf = w->Ap = w->x = w->b = w->partial = w->gsum = w->hist = w->tot = nullptr;
     w->st = nullptr;
     w->ended = nullptr;
     w->cap = 0;
@@ -552,6 +609,8 @@ void drop_workspace(const hpccg_hip_matrix* M)
     if (w->h_ended) (void)hipHostFree(w->h_ended);
     if (w->ev0) (void)hipEventDestroy(w->ev0);
     if (w->ev1) (void)hipEventDestroy(w->ev1);
+    if (w->evr) (void)hipEventDestroy(w->evr);
+    if (w->evs) (void)hipEventDestroy(w->evs);
     delete w;
 }
 
@@ -600,6 +659,8 @@ int get_workspace(hpccg_hip_matrix* M, const MatrixView& v, int ncols, int max_i
     if (!w->h_ended) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&w->h_ended), sizeof(int), hipHostMallocDefault));
     if (!w->ev0) HIP_TRY(hipEventCreate(&w->ev0));
     if (!w->ev1) HIP_TRY(hipEventCreate(&w->ev1));
+    if (v.in_group && !w->evr) HIP_TRY(hipEventCreateWithFlags(&w->evr, hipEventDisableTiming));
+    if (v.in_group && !w->evs) HIP_TRY(hipEventCreateWithFlags(&w->evs, hipEventDisableTiming));
     const long long hneed = (long long)max_iter + 1;
     if (ncols <= w->cap && hneed <= w->hstride) return 0;
     const int cap = std::max(ncols, w->cap);
@@ -607,10 +668,18 @@ int get_workspace(hpccg_hip_matrix* M, const MatrixView& v, int ncols, int max_i
     free_device(w);
     const size_t npad = (size_t)v.npad;
     const size_t ng = (size_t)(v.nslices + kGroup - 1) / kGroup;
-    w->pcs = (long long)(npad + 2 * (size_t)v.guard_rows);
+    // a p column: [guard | ghost_lo (padded) | local rows (padded) | ghost_hi's spill (padded) | guard].
+    // The ghost_hi rows start at local row n (where the single solve's p has
+    // them): inside the last slice's padding rows and, past npad, in ghi_pad.
+    // glo_pad is whole slices, so local row 0 keeps the buffer's alignment.
+    const size_t glo_pad = ((size_t)v.ghost_lo + kSliceRows - 1) / kSliceRows * kSliceRows;
+    const size_t ghi_pad = v.ghost_hi ? ((size_t)v.ghost_hi + 2 + kSliceRows - 1) / kSliceRows * kSliceRows : 0;
+    w->p0 = (long long)((size_t)v.guard_rows + glo_pad);
+    w->pcs = (long long)(npad + glo_pad + ghi_pad + 2 * (size_t)v.guard_rows);
     w->vcs = (long long)npad;
     // zeroed: the guard zones and the rows past n of p and r are read (holes,
-    // full-width loads) and never stored
+    // full-width loads) and never stored by a kernel (p's ghost rows: by the
+    // group's halo copies only)
     int rc = alloc_zero(w, &w->pbuf, (size_t)w->pcs * cap);
     if (!rc) rc = alloc_zero(w, &w->rbuf, (size_t)w->pcs * cap);
     if (!rc) rc = alloc_zero(w, &w->Ap, npad * cap);
@@ -619,6 +688,7 @@ int get_workspace(hpccg_hip_matrix* M, const MatrixView& v, int ncols, int max_i
     if (!rc) rc = alloc_zero(w, &w->partial, 2 * (size_t)cap * std::max(v.nslices, 1));
     if (!rc) rc = alloc_zero(w, &w->gsum, 2 * (size_t)cap * std::max<size_t>(ng, 1));
     if (!rc) rc = alloc_zero(w, &w->st, (size_t)cap);
+    if (!rc && v.in_group) rc = alloc_zero(w, &w->tot, 2 * (size_t)cap);
     if (!rc) rc = alloc_zero(w, &w->ended, 1);
     if (!rc) rc = alloc_zero(w, &w->hist, (size_t)cap * (size_t)hstride);
     if (rc) {
@@ -630,11 +700,12 @@ int get_workspace(hpccg_hip_matrix* M, const MatrixView& v, int ncols, int max_i
     return 0;
 }
 
-// What the batch runs on: one rank, no halo.
-int check_matrix(hpccg_hip_matrix* M, MatrixView* v)
+// What the batch runs on: one rank, no halo (group1: also the one member of a
+// one-rank in-process group, which is that).
+int check_matrix(hpccg_hip_matrix* M, MatrixView* v, bool group1 = false)
 {
     TRY(hpccg_hip_internal_view(M, v));
-    if (v->in_group) return fail(HPCCG_HIP_EINVAL, "batch: the matrix is a member of an in-process group (one rank only)");
+    if (v->in_group && !(group1 && v->nranks == 1)) return fail(HPCCG_HIP_EINVAL, "batch: the matrix is a member of an in-process group (one rank only)");
     if (v->nranks > 1) return fail(HPCCG_HIP_EINVAL, "batch: the matrix belongs to a communicator of %d ranks (one rank only)", v->nranks);
     if (v->ghost_lo || v->ghost_hi) return fail(HPCCG_HIP_EINVAL, "batch: the matrix has halo rows (one rank only)");
     if (!v->has_a && !v->has_sell) return fail(HPCCG_HIP_EINVAL, "batch: the matrix holds no device image");
@@ -657,8 +728,10 @@ BatchArgs make_args(const Workspace* w, int nrhs, int max_iter, double tol)
     a.nt = v.nt;
     a.a_width = v.a_width;
     a.tri = std::getenv("HPCCG_BATCH_NO_TRIPLES") ? 0 : 1;  // diagnostics: A/B of the x-triple plan
-    a.p =w->pbuf + v.guard_rows;
-    a.r = w->rbuf + v.guard_rows;
+    a.p = w->pbuf + w->p0;
+    a.r = w->rbuf + w->p0;
+    a.xsell = v.sell_col_base;
+    a.tot = w->tot;
     a.Ap = w->Ap;
     a.x = w->x;
     a.b = w->b;
@@ -746,9 +819,9 @@ void launch_update(const Workspace* w, BatchArgs a, bool prologue)
     });
 }
 
-void launch_finalize(const Workspace* w, const BatchArgs& a, int which)
+void launch_finalize(const Workspace* w, const BatchArgs& a, int which, int local = 0)
 {
-    hipLaunchKernelGGL(k_batch_finalize, dim3(a.nrhs), dim3(kFinThreads), 0, w->v.stream, a, which);
+    hipLaunchKernelGGL(k_batch_finalize, dim3(a.nrhs), dim3(kFinThreads), 0, w->v.stream, a, which, local);
 }
 
 // Columns between the caller's column-major array and the workspace (kind:
@@ -761,6 +834,8 @@ int copy_cols(const Workspace* w, double* dst, long long ldd, const double* src,
                                sizeof(double) * (size_t)w->v.n, kind, w->v.stream));
     return 0;
 }
+
+int read_results(Workspace* w, int nrhs, int* niters, double* normr, double* wall);
 
 // The batch CG on the columns staged in the workspace's b and x.
 int run_cg(Workspace* w, int nrhs, int max_iter, double tol, int* niters, double* normr, double* wall)
@@ -788,6 +863,14 @@ int run_cg(Workspace* w, int nrhs, int max_iter, double tol, int* niters, double
         }
     }
     HIP_TRY(hipGetLastError());
+    return read_results(w, nrhs, niters, normr, wall);
+}
+
+// The end of a batch CG on w's stream (a group: member 0's, whose last launch
+// followed every member's): its wall time, the columns' states and traces.
+int read_results(Workspace* w, int nrhs, int* niters, double* normr, double* wall)
+{
+    hipStream_t s = w->v.stream;
     HIP_TRY(hipEventRecord(w->ev1, s));
     std::vector<ColState> st(nrhs);
     std::vector<double> hist((size_t)nrhs * (size_t)w->hstride);
@@ -825,11 +908,11 @@ int check_solve_args(hpccg_hip_matrix* M, int nrhs, const double* B, long long l
 }
 
 int solve_common(hpccg_hip_matrix* M, int nrhs, const double* B, long long ldb, double* X, long long ldx, int max_iter,
-                 double tol, int* niters, double* normr, double* times, bool host)
+                 double tol, int* niters, double* normr, double* times, bool host, bool group1 = false)
 {
     TRY(check_solve_args(M, nrhs, B, ldb, X, ldx, max_iter, niters, normr));
     MatrixView v;
-    TRY(check_matrix(M, &v));
+    TRY(check_matrix(M, &v, group1));
     if (ldb < v.n || ldx < v.n)
         return fail(HPCCG_HIP_EINVAL, "batch: leading dimensions %lld, %lld below the %d rows", ldb, ldx, v.n);
     if (times) std::fill(times, times + 7, 0.0);
@@ -876,6 +959,319 @@ int solve_common(hpccg_hip_matrix* M, int nrhs, const double* B, long long ldb, 
     return 0;
 }
 
+// Y(:,c) = A X(:,c) on one rank.
+int sparsemv_one(hpccg_hip_matrix* M, int nrhs, const double* X_dev, long long ldx, double* Y_dev, long long ldy,
+                 bool group1)
+{
+    if (!M || !X_dev || !Y_dev) return fail(HPCCG_HIP_EINVAL, "batch: NULL argument");
+    if (nrhs <= 0) return fail(HPCCG_HIP_EINVAL, "batch: nrhs %d (at least 1)", nrhs);
+    MatrixView v;
+    TRY(check_matrix(M, &v, group1));
+    if (ldx < v.n || ldy < v.n)
+        return fail(HPCCG_HIP_EINVAL, "batch: leading dimensions %lld, %lld below the %d rows", ldx, ldy, v.n);
+    if (v.n == 0) return 0;
+    if (nrhs == 1) return hpccg_hip_sparsemv(M, X_dev, Y_dev);
+    Workspace* w = nullptr;
+    TRY(get_workspace(M, v, nrhs, 1, &w));
+    // x into the guarded p columns, Ap = A p, Ap out
+    BatchArgs a = make_args(w, nrhs, 1, 0.0);
+    a.force = 1;
+    TRY(copy_cols(w, a.p, w->pcs, X_dev, ldx, nrhs, hipMemcpyDeviceToDevice));
+    launch_spmm(w, a, true);
+    HIP_TRY(hipGetLastError());
+    TRY(copy_cols(w, Y_dev, ldy, w->Ap, w->vcs, nrhs, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipStreamSynchronize(v.stream));
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// In-process rank group (include/hpccg_hip_batch_group.h): member r is rank r
+// of a z-slab job; every member runs the batch kernels on its own stream with
+// its own workspace, the ghost planes of every column's p move by copies
+// between the members, and the two dots are summed over the members in rank
+// order by k_batch_group_sum on member 0's stream.
+// ---------------------------------------------------------------------------
+struct Group {
+    int P = 0;
+    std::vector<MatrixView> v;
+    std::vector<Workspace*> w;
+    std::vector<BatchArgs> a;
+};
+
+// The whole group in rank order, z-slab plan, a device image on every member.
+// Reads the matrices' records only: no device work.
+int check_group(hpccg_hip_matrix* const* Ms, int nranks, Group* G)
+{
+    G->P = nranks;
+    G->v.resize(nranks);
+    for (int r = 0; r < nranks; r++) {
+        if (!Ms[r]) return fail(HPCCG_HIP_EINVAL, "group batch: Ms[%d] is NULL", r);
+        TRY(hpccg_hip_internal_view(Ms[r], &G->v[r]));
+        const MatrixView& v = G->v[r];
+        if (v.nranks != nranks || v.rank != r || (nranks > 1 && !v.in_group))
+            return fail(HPCCG_HIP_EINVAL, "group batch: Ms[%d] is not rank %d of a %d-rank in-process group", r, r,
+                        nranks);
+        if (nranks > 1 && v.group_id != G->v[0].group_id)
+            return fail(HPCCG_HIP_EINVAL, "group batch: Ms[%d] is a member of another group than Ms[0]", r);
+    }
+    if (nranks == 1) return 0;  // (the single-rank batch checks its matrix itself)
+    for (int r = 0; r < nranks; r++) {
+        const MatrixView& v = G->v[r];
+        if (v.general)
+            return fail(HPCCG_HIP_EPLAN, "group batch: member %d uses the gather plan (z-slab plan members only)", r);
+        // the halo copies below rely on these (hpccg_slab_plan made them so)
+        const int lo_max = r > 0 ? G->v[r - 1].n : 0, hi_max = r < nranks - 1 ? G->v[r + 1].n : 0;
+        if (v.ghost_lo < 0 || v.ghost_hi < 0 || v.ghost_lo > lo_max || v.ghost_hi > hi_max)
+            return fail(HPCCG_HIP_EPLAN, "group batch: member %d's ghost rows (%d, %d) are not its neighbours' rows", r,
+                        v.ghost_lo, v.ghost_hi);
+        if (v.n <= 0) return fail(HPCCG_HIP_EINVAL, "group batch: member %d has no rows", r);
+        if (!v.has_a && !v.has_sell) return fail(HPCCG_HIP_EINVAL, "group batch: member %d holds no device image", r);
+    }
+    return 0;
+}
+
+int check_group_lds(const Group& G, const long long* l0, const long long* l1, const char* what)
+{
+    for (int r = 0; r < G.P; r++)
+        if (l0[r] < G.v[r].n || l1[r] < G.v[r].n)
+            return fail(HPCCG_HIP_EINVAL, "group batch: member %d's leading dimensions (%s) %lld, %lld below its %d rows",
+                        r, what, l0[r], l1[r], G.v[r].n);
+    return 0;
+}
+
+int use(const Group& G, int r)
+{
+    HIP_TRY(hipSetDevice(G.v[r].device));
+    return 0;
+}
+
+int group_workspaces(hpccg_hip_matrix* const* Ms, Group* G, int nrhs, int max_iter, double tol)
+{
+    G->w.assign(G->P, nullptr);
+    G->a.resize(G->P);
+    for (int r = 0; r < G->P; r++) {
+        TRY(get_workspace(Ms[r], G->v[r], nrhs, max_iter, &G->w[r]));
+        G->a[r] = make_args(G->w[r], nrhs, max_iter, tol);
+    }
+    return 0;
+}
+
+// rows of one member's column into another's (one device: a plain copy)
+int member_copy(const MatrixView& dv, double* dst, const MatrixView& sv, const double* src, size_t n)
+{
+    if (dv.device == sv.device)
+        HIP_TRY(hipMemcpyAsync(dst, src, sizeof(double) * n, hipMemcpyDeviceToDevice, dv.stream));
+    else
+        HIP_TRY(hipMemcpyPeerAsync(dst, dv.device, src, sv.device, sizeof(double) * n, dv.stream));
+    return 0;
+}
+
+// The halo of every column's p (group_halo in hpccg_solver.cpp, per column):
+// member r's ghost_lo rows are member r - 1's last rows, its ghost_hi rows
+// (from local row n) member r + 1's first, copied on r's stream once the
+// neighbour's stream has stored them (its event). Frozen columns' planes are
+// copied too (their p no longer changes: harmless).
+// p is one buffer per column, not a ring. A neighbour cannot overwrite its p
+// before these copies have read it: its next k_batch_p follows the group sum of
+// p.Ap (in the prologue: of r.r) on its stream, that sum waits for every
+// member's SpMM, and each member's SpMM follows its copies on its own stream.
+int group_halo(const Group& G, int nrhs)
+{
+    for (int r = 0; r < G.P; r++) {
+        TRY(use(G, r));
+        HIP_TRY(hipEventRecord(G.w[r]->evr, G.v[r].stream));
+    }
+    for (int r = 0; r < G.P; r++) {
+        const MatrixView& v = G.v[r];
+        const BatchArgs& a = G.a[r];
+        TRY(use(G, r));
+        if (r > 0 && v.ghost_lo) {
+            const BatchArgs& l = G.a[r - 1];
+            HIP_TRY(hipStreamWaitEvent(v.stream, G.w[r - 1]->evr, 0));
+            for (int c = 0; c < nrhs; c++)
+                TRY(member_copy(v, a.p + (long long)c * a.pcs - v.ghost_lo, G.v[r - 1],
+                                l.p + (long long)c * l.pcs + (l.n - v.ghost_lo), (size_t)v.ghost_lo));
+        }
+        if (r < G.P - 1 && v.ghost_hi) {
+            const BatchArgs& u = G.a[r + 1];
+            HIP_TRY(hipStreamWaitEvent(v.stream, G.w[r + 1]->evr, 0));
+            for (int c = 0; c < nrhs; c++)
+                TRY(member_copy(v, a.p + (long long)c * a.pcs + a.n, G.v[r + 1], u.p + (long long)c * u.pcs,
+                                (size_t)v.ghost_hi));
+        }
+    }
+    return 0;
+}
+
+// The global dot `which` of every running column and its state on every
+// member: member 0's stream waits for every member's local finalize, runs
+// k_batch_group_sum, and the other members' streams wait for it.
+int group_sum(const Group& G, const GroupTotals& gt, int which, int nrhs)
+{
+    for (int r = 1; r < G.P; r++) {
+        TRY(use(G, r));
+        HIP_TRY(hipEventRecord(G.w[r]->evr, G.v[r].stream));
+    }
+    TRY(use(G, 0));
+    hipStream_t s0 = G.v[0].stream;
+    for (int r = 1; r < G.P; r++) HIP_TRY(hipStreamWaitEvent(s0, G.w[r]->evr, 0));
+    hipLaunchKernelGGL(k_batch_group_sum, dim3((nrhs + 63) / 64), dim3(64), 0, s0, G.a[0], gt, which);
+    HIP_TRY(hipEventRecord(G.w[0]->evs, s0));
+    for (int r = 1; r < G.P; r++) {
+        TRY(use(G, r));
+        HIP_TRY(hipStreamWaitEvent(G.v[r].stream, G.w[0]->evs, 0));
+    }
+    return 0;
+}
+
+// The batch CG over the group on the columns staged in the members' b and x.
+int group_run_cg(const Group& G, int nrhs, int max_iter, int* niters, double* normr, double* wall)
+{
+    GroupTotals gt;
+    std::memset(&gt, 0, sizeof gt);
+    gt.nranks = G.P;
+    for (int r = 0; r < G.P; r++) {
+        gt.cap[r] = G.w[r]->cap;
+        gt.tot[r] = G.w[r]->tot;
+        gt.st[r] = G.w[r]->st;
+    }
+    Workspace* w0 = G.w[0];
+    TRY(use(G, 0));
+    HIP_TRY(hipEventRecord(w0->ev0, G.v[0].stream));
+    for (int r = 0; r < G.P; r++) {
+        TRY(use(G, r));
+        hipLaunchKernelGGL(k_batch_init, dim3((nrhs + 63) / 64), dim3(64), 0, G.v[r].stream, G.a[r]);
+        launch_p(G.w[r], G.a[r], true);
+    }
+    TRY(group_halo(G, nrhs));
+    for (int r = 0; r < G.P; r++) {
+        TRY(use(G, r));
+        launch_spmm(G.w[r], G.a[r], true);
+        launch_update(G.w[r], G.a[r], true);
+        launch_finalize(G.w[r], G.a[r], kDotRR, 1);
+    }
+    TRY(group_sum(G, gt, kDotRR, nrhs));
+    HIP_TRY(hipGetLastError());
+    for (int k = 1; k < max_iter; k++) {
+        for (int r = 0; r < G.P; r++) {
+            TRY(use(G, r));
+            launch_p(G.w[r], G.a[r], false);
+        }
+        TRY(group_halo(G, nrhs));
+        for (int r = 0; r < G.P; r++) {
+            TRY(use(G, r));
+            launch_spmm(G.w[r], G.a[r], false);
+            launch_finalize(G.w[r], G.a[r], kDotPAP, 1);
+        }
+        TRY(group_sum(G, gt, kDotPAP, nrhs));
+        for (int r = 0; r < G.P; r++) {
+            TRY(use(G, r));
+            launch_update(G.w[r], G.a[r], false);
+            launch_finalize(G.w[r], G.a[r], kDotRR, 1);
+        }
+        TRY(group_sum(G, gt, kDotRR, nrhs));
+        if (k % kCheckEvery == 0 && k + 1 < max_iter) {
+            HIP_TRY(hipGetLastError());
+            TRY(use(G, 0));
+            HIP_TRY(hipMemcpyAsync(w0->h_ended, w0->ended, sizeof(int), hipMemcpyDeviceToHost, G.v[0].stream));
+            HIP_TRY(hipStreamSynchronize(G.v[0].stream));
+            if (*w0->h_ended >= nrhs) break;  // every column is frozen on every member
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    TRY(use(G, 0));
+    TRY(read_results(w0, nrhs, niters, normr, wall));
+    for (int r = 1; r < G.P; r++) {  // (the last sum's event was their streams' last wait)
+        TRY(use(G, r));
+        HIP_TRY(hipStreamSynchronize(G.v[r].stream));
+    }
+    return 0;
+}
+
+int group_solve(hpccg_hip_matrix* const* Ms, const Group& G0, int nrhs, const double* const* B, const long long* ldb,
+                double* const* X, const long long* ldx, int max_iter, double tol, int* niters, double* normr,
+                double* times)
+{
+    Group G = G0;
+    if (times) std::fill(times, times + 7, 0.0);
+    if (nrhs == 1) {  // the group solve itself; its trace kept with member 0's record
+        double t1[7] = {0, 0, 0, 0, 0, 0, 0};
+        TRY(hpccg_hip_group_solve(Ms, G.P, B, X, max_iter, tol, niters, normr, t1));
+        if (times) times[0] = t1[0];
+        Workspace* w = nullptr;
+        TRY(get_workspace(Ms[0], G.v[0], 0, 0, &w));
+        w->trace.assign(1, {});
+        std::vector<double>& tr = w->trace[0];
+        tr.assign((size_t)niters[0] + 1, 0.0);
+        const int got = hpccg_hip_last_trace(Ms[0], tr.data(), (int)tr.size());
+        tr.resize((size_t)std::max(got, 0));
+        return 0;
+    }
+    if (max_iter < 1) max_iter = 1;
+    TRY(group_workspaces(Ms, &G, nrhs, max_iter, tol));
+    for (int r = 0; r < G.P; r++) {
+        TRY(use(G, r));
+        TRY(copy_cols(G.w[r], G.w[r]->b, G.w[r]->vcs, B[r], ldb[r], nrhs, hipMemcpyDeviceToDevice));
+        TRY(copy_cols(G.w[r], G.w[r]->x, G.w[r]->vcs, X[r], ldx[r], nrhs, hipMemcpyDeviceToDevice));
+    }
+    double wall = 0.0;
+    TRY(group_run_cg(G, nrhs, max_iter, niters, normr, &wall));
+    for (int r = 0; r < G.P; r++) {
+        TRY(use(G, r));
+        TRY(copy_cols(G.w[r], X[r], ldx[r], G.w[r]->x, G.w[r]->vcs, nrhs, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipStreamSynchronize(G.v[r].stream));
+    }
+    if (times) times[0] = wall;
+    return 0;
+}
+
+int group_sparsemv(hpccg_hip_matrix* const* Ms, const Group& G0, int nrhs, const double* const* X,
+                   const long long* ldx, double* const* Y, const long long* ldy)
+{
+    Group G = G0;
+    TRY(group_workspaces(Ms, &G, nrhs, 1, 0.0));
+    // x into the local rows of the p columns, their halo, Ap = A p, Ap out
+    for (int r = 0; r < G.P; r++) {
+        G.a[r].force = 1;
+        TRY(use(G, r));
+        TRY(copy_cols(G.w[r], G.a[r].p, G.w[r]->pcs, X[r], ldx[r], nrhs, hipMemcpyDeviceToDevice));
+    }
+    TRY(group_halo(G, nrhs));
+    for (int r = 0; r < G.P; r++) {
+        TRY(use(G, r));
+        launch_spmm(G.w[r], G.a[r], true);
+        HIP_TRY(hipGetLastError());
+        TRY(copy_cols(G.w[r], Y[r], ldy[r], G.w[r]->Ap, G.w[r]->vcs, nrhs, hipMemcpyDeviceToDevice));
+    }
+    // (every member's copies of its neighbours' rows are done before any
+    // member's buffers may be reused by the next call)
+    for (int r = 0; r < G.P; r++) {
+        TRY(use(G, r));
+        HIP_TRY(hipStreamSynchronize(G.v[r].stream));
+    }
+    return 0;
+}
+
+// f() with the caller's current device put back afterwards
+template <class F>
+int keep_device(F f)
+{
+    int cur = 0;
+    HIP_TRY(hipGetDevice(&cur));
+    const int rc = f();
+    (void)hipSetDevice(cur);
+    return rc;
+}
+
+int check_group_args(hpccg_hip_matrix* const* Ms, int nranks, int nrhs)
+{
+    if (!Ms) return fail(HPCCG_HIP_EINVAL, "group batch: Ms is NULL");
+    if (nranks < 1 || nranks > kMaxMembers)
+        return fail(HPCCG_HIP_EINVAL, "group batch: nranks %d (1 to %d members)", nranks, kMaxMembers);
+    if (nrhs <= 0) return fail(HPCCG_HIP_EINVAL, "group batch: nrhs %d (at least 1)", nrhs);
+    return 0;
+}
+
 }  // namespace
 
 }  // namespace hpccg
@@ -915,25 +1311,7 @@ int hpccg_hip_batch_last_trace(const hpccg_hip_matrix* M, int col, double* out, 
 int hpccg_hip_batch_sparsemv(hpccg_hip_matrix* M, int nrhs, const double* X_dev, long long ldx, double* Y_dev,
                              long long ldy)
 {
-    if (!M || !X_dev || !Y_dev) return fail(HPCCG_HIP_EINVAL, "batch: NULL argument");
-    if (nrhs <= 0) return fail(HPCCG_HIP_EINVAL, "batch: nrhs %d (at least 1)", nrhs);
-    MatrixView v;
-    TRY(check_matrix(M, &v));
-    if (ldx < v.n || ldy < v.n)
-        return fail(HPCCG_HIP_EINVAL, "batch: leading dimensions %lld, %lld below the %d rows", ldx, ldy, v.n);
-    if (v.n == 0) return 0;
-    if (nrhs == 1) return hpccg_hip_sparsemv(M, X_dev, Y_dev);
-    Workspace* w = nullptr;
-    TRY(get_workspace(M, v, nrhs, 1, &w));
-    // x into the guarded p columns, Ap = A p, Ap out
-    BatchArgs a = make_args(w, nrhs, 1, 0.0);
-    a.force = 1;
-    TRY(copy_cols(w, a.p, w->pcs, X_dev, ldx, nrhs, hipMemcpyDeviceToDevice));
-    launch_spmm(w, a, true);
-    HIP_TRY(hipGetLastError());
-    TRY(copy_cols(w, Y_dev, ldy, w->Ap, w->vcs, nrhs, hipMemcpyDeviceToDevice));
-    HIP_TRY(hipStreamSynchronize(v.stream));
-    return 0;
+    return sparsemv_one(M, nrhs, X_dev, ldx, Y_dev, ldy, false);
 }
 
 int hpccg_hip_batch_release(hpccg_hip_matrix* M)
@@ -957,6 +1335,59 @@ int hpccg_hip_batch_live_workspaces(int* count)
     std::lock_guard<std::mutex> lk(g_mu);
     *count = (int)g_ws.size();
     return 0;
+}
+
+// ---- include/hpccg_hip_batch_group.h ---------------------------------------
+int hpccg_hip_group_batch_abi_version(void) { return 1; }
+
+int hpccg_hip_group_batch_solve_device(hpccg_hip_matrix* const* Ms, int nranks, int nrhs, const double* const* B_dev,
+                                       const long long* ldb, double* const* X_dev, const long long* ldx, int max_iter,
+                                       double tolerance, int* niters, double* normr, double* times)
+{
+    TRY(check_group_args(Ms, nranks, nrhs));
+    if (max_iter < 0) return fail(HPCCG_HIP_EINVAL, "group batch: max_iter %d is negative", max_iter);
+    if (!B_dev || !ldb || !X_dev || !ldx || !niters || !normr)
+        return fail(HPCCG_HIP_EINVAL, "group batch: NULL argument (B_dev, ldb, X_dev, ldx, niters or normr)");
+    for (int r = 0; r < nranks; r++)
+        if (!B_dev[r] || !X_dev[r]) return fail(HPCCG_HIP_EINVAL, "group batch: B_dev[%d] or X_dev[%d] is NULL", r, r);
+    Group G;
+    TRY(check_group(Ms, nranks, &G));
+    TRY(check_group_lds(G, ldb, ldx, "ldb, ldx"));
+    return keep_device([&] {
+        if (nranks == 1)
+            return solve_common(Ms[0], nrhs, B_dev[0], ldb[0], X_dev[0], ldx[0], max_iter, tolerance, niters, normr,
+                                times, false, true);
+        return group_solve(Ms, G, nrhs, B_dev, ldb, X_dev, ldx, max_iter, tolerance, niters, normr, times);
+    });
+}
+
+int hpccg_hip_group_batch_sparsemv(hpccg_hip_matrix* const* Ms, int nranks, int nrhs, const double* const* X_dev,
+                                   const long long* ldx, double* const* Y_dev, const long long* ldy)
+{
+    TRY(check_group_args(Ms, nranks, nrhs));
+    if (!X_dev || !ldx || !Y_dev || !ldy)
+        return fail(HPCCG_HIP_EINVAL, "group batch: NULL argument (X_dev, ldx, Y_dev or ldy)");
+    for (int r = 0; r < nranks; r++)
+        if (!X_dev[r] || !Y_dev[r]) return fail(HPCCG_HIP_EINVAL, "group batch: X_dev[%d] or Y_dev[%d] is NULL", r, r);
+    Group G;
+    TRY(check_group(Ms, nranks, &G));
+    TRY(check_group_lds(G, ldx, ldy, "ldx, ldy"));
+    return keep_device([&] {
+        if (nranks == 1) return sparsemv_one(Ms[0], nrhs, X_dev[0], ldx[0], Y_dev[0], ldy[0], true);
+        return group_sparsemv(Ms, G, nrhs, X_dev, ldx, Y_dev, ldy);
+    });
+}
+
+int hpccg_hip_group_batch_last_trace(hpccg_hip_matrix* const* Ms, int nranks, int col, double* out, int cap)
+{
+    if (!Ms) return fail(HPCCG_HIP_EINVAL, "group batch: Ms is NULL");
+    if (nranks < 1 || nranks > kMaxMembers)
+        return fail(HPCCG_HIP_EINVAL, "group batch: nranks %d (1 to %d members)", nranks, kMaxMembers);
+    if (!out) return fail(HPCCG_HIP_EINVAL, "group batch: out is NULL");
+    Group G;
+    TRY(check_group(Ms, nranks, &G));
+    // one set of all-reduced scalars: kept with member 0's record
+    return hpccg_hip_batch_last_trace(Ms[0], col, out, cap);
 }
 
 }  // extern "C"

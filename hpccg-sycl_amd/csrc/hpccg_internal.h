@@ -331,6 +331,9 @@ struct MatrixView {
     long long npad;        // rows of every padded vector (a multiple of kSliceRows)
     int nranks;            // z-slab ranks of the matrix's communicator or group
     int in_group;          // 1: a member of an in-process group
+    int rank;              // the matrix's z-slab rank (a group member: its index in the group)
+    unsigned long long group_id;  // the in-process group the matrix was made in (0: none)
+    int general;           // 1: the halo plan is the gather plan (externals after the local rows)
     int ghost_lo, ghost_hi;  // halo rows below / above
     // SELL-512-A (has_a): values in per-slice offset-aligned slots
     int has_a;
@@ -344,6 +347,7 @@ struct MatrixView {
     const unsigned int* slice_base;
     const int* cols;
     const double* vals;
+    long long sell_col_base;  // SELL-512 column 0 relative to local row 0 (-ghost_lo: the columns count the ghosts)
     long long guard_rows;  // kGuardRows: the zeroed zone on each side of p and r
     long long pstride;     // distance between the single solve's p buffers (doubles)
     hipStream_t stream;    // the matrix's stream

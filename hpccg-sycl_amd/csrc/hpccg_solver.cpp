@@ -278,6 +278,7 @@ struct hpccg_hip_matrix {
     int device = 0;
     int rank = 0, nranks = 1;  // z-slab rank of this matrix (RCCL communicator or in-process group)
     int in_group = 0;          // 1: halo / all-reduce by hpccg_hip_group_solve, not RCCL
+    unsigned long long group_id = 0;  // the in-process group this member was made in (0: none)
     int nrow = 0, start_row = 0, total_nrow = 0;
     int ghost_lo = 0, ghost_hi = 0;
     int send_lo = 0;  // rows to send to rank-1 (its ghost_hi)
@@ -3373,6 +3374,8 @@ unsigned long long fingerprint(const HPC_Sparse_Matrix* A)
 // ---- in-process rank group -------------------------------------------------
 namespace {
 
+std::atomic<unsigned long long> g_next_group{0};  // ids of the groups made (hpccg_hip_matrix::group_id)
+
 template <class Make>
 int group_make(int nranks, const int* devices, hpccg_hip_matrix** out, Make make, const int* info = nullptr,
                const std::vector<GatherPlan>* plans = nullptr)
@@ -3433,7 +3436,10 @@ int group_make(int nranks, const int* devices, hpccg_hip_matrix** out, Make make
             free_matrix(out[r]);
             out[r] = nullptr;
         }
+        return rc;
     }
+    const unsigned long long id = ++g_next_group;
+    for (int r = 0; r < nranks; r++) out[r]->group_id = id;
     return rc;
 }
 
@@ -3848,6 +3854,9 @@ int hpccg_hip_internal_view(const hpccg_hip_matrix* M, MatrixView* out)
     v.npad = (long long)M->npad;
     v.nranks = M->nranks;
     v.in_group = M->in_group;
+    v.rank = M->rank;
+    v.group_id = M->group_id;
+    v.general = M->general;
     v.ghost_lo = M->ghost_lo;
     v.ghost_hi = M->ghost_hi;
     v.has_a = M->has_a;
@@ -3860,6 +3869,7 @@ int hpccg_hip_internal_view(const hpccg_hip_matrix* M, MatrixView* out)
     v.slice_base = M->d_slice_base;
     v.cols = M->d_cols;
     v.vals = M->d_vals;
+    v.sell_col_base = -(long long)M->ghost_lo;
     v.guard_rows = kGuardRows;
     v.pstride = M->pstride;
     v.stream = M->stream;

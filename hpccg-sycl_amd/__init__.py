@@ -190,6 +190,56 @@ def batch_lib() -> C.CDLL:
     return L
 
 
+MIXED_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_mixed.so")
+_mixed_lib = None
+
+
+def mixed_lib() -> C.CDLL:
+    """Load libhpccg_hip_mixed.so (include/hpccg_hip_mixed.h) on first use. It
+    is linked against libhpccg_hip.so beside it, so lib() is loaded first and
+    both share one copy of the main library."""
+    global _mixed_lib
+    if _mixed_lib is not None:
+        return _mixed_lib
+    if os.environ.get("HPCCG_HIP_LIB", LIB_PATH) != LIB_PATH:
+        raise HPCCGError("the mixed library runs on the in-tree libhpccg_hip.so only (HPCCG_HIP_LIB is set)")
+    lib()
+    if not os.path.exists(MIXED_LIB_PATH):
+        raise HPCCGError(f"{MIXED_LIB_PATH} missing: run build() (the mixed solve has no fallback)")
+    try:
+        L = C.CDLL(MIXED_LIB_PATH)
+    except OSError as e:
+        raise HPCCGError(f"{MIXED_LIB_PATH} does not load: {e}") from e
+    vp, ip, dp, lp = C.c_void_p, C.c_int, C.c_double, C.c_longlong
+    PI, PD = C.POINTER(C.c_int), C.POINTER(C.c_double)
+    sig = {
+        "hpccg_hip_mixed_abi_version": (ip, []),
+        "hpccg_hip_mixed_solve_device": (ip, [vp, ip, vp, lp, vp, lp, ip, dp, ip, dp, PI, PD, PD]),
+        "hpccg_hip_mixed_solve": (ip, [vp, ip, vp, lp, vp, lp, ip, dp, ip, dp, PI, PD, PD]),
+        "hpccg_hip_mixed_sparsemv": (ip, [vp, ip, vp, lp, vp, lp]),
+        "hpccg_hip_mixed_info": (ip, [vp, C.POINTER(lp)]),
+        "hpccg_hip_mixed_last_trace": (ip, [vp, ip, PD, ip]),
+        "hpccg_hip_mixed_last_sweeps": (ip, [vp, ip, PI, PD, ip]),
+        "hpccg_hip_mixed_release": (ip, [vp]),
+        "hpccg_hip_mixed_workspace_bytes": (ip, [vp, C.POINTER(lp)]),
+        "hpccg_hip_mixed_live_workspaces": (ip, [PI]),
+    }
+    for name, (res, args) in sig.items():
+        f = getattr(L, name)
+        f.restype = res
+        f.argtypes = args
+    _mixed_lib = L
+    return L
+
+
+def mixed_exported_symbols() -> list[str]:
+    """Functions include/hpccg_hip_mixed.h declares (checked by the CPU suite)."""
+    import re
+    with open(os.path.join(ROOT, "include", "hpccg_hip_mixed.h")) as f:
+        text = f.read()
+    return sorted(set(re.findall(r"\b(hpccg_hip_mixed_\w+)\s*\(", text)))
+
+
 def batch_exported_symbols() -> list[str]:
     """Functions include/hpccg_hip_batch.h declares (checked by the CPU suite)."""
     import re
@@ -470,6 +520,48 @@ class Matrix:
         _check(_batch_lib.hpccg_hip_batch_workspace_bytes(self.h, C.byref(v)), "batch_workspace_bytes")
         return v.value
 
+    def mixed_info(self) -> dict:
+        """The fp32 image of this matrix (built on first use): exact (every
+        value survives double -> float -> double: the mixed solve is then
+        bitwise the fp64 solve), its device bytes, the device bytes of the rest
+        of the mixed workspace, and the values that did not survive."""
+        a = (C.c_longlong * 4)()
+        _check(mixed_lib().hpccg_hip_mixed_info(self.h, a), "mixed_info")
+        return {"exact": int(a[0]), "image_bytes": int(a[1]), "workspace_bytes": int(a[2]), "inexact_values": int(a[3])}
+
+    def last_trace_mixed(self, col: int, cap: int = 100000) -> np.ndarray:
+        """The inner recurrences' normr of column col of the last HPCCG_mixed on
+        this matrix, sweep after sweep (it_s + 1 entries each)."""
+        out = np.zeros(cap, np.float64)
+        n = mixed_lib().hpccg_hip_mixed_last_trace(self.h, int(col), out.ctypes.data_as(C.POINTER(C.c_double)), cap)
+        if n < 0:
+            _check(n, "last_trace_mixed")
+        return out[:n]
+
+    def last_sweeps_mixed(self, col: int, cap: int = 4096):
+        """(iters, resid) of column col of the last HPCCG_mixed: the inner
+        iterations of every sweep, and the fp64 residual norm before every
+        sweep with the final one appended (len(resid) == len(iters) + 1)."""
+        it = np.zeros(cap, np.int32)
+        rs = np.zeros(cap, np.float64)
+        n = mixed_lib().hpccg_hip_mixed_last_sweeps(self.h, int(col), it.ctypes.data_as(C.POINTER(C.c_int)),
+                                                    rs.ctypes.data_as(C.POINTER(C.c_double)), cap)
+        if n < 0:
+            _check(n, "last_sweeps_mixed")
+        return it[:n], rs[:n + 1]
+
+    def mixed_release(self) -> None:
+        """Free this matrix's mixed workspace and fp32 image now (close() does it too)."""
+        if self.h and _mixed_lib is not None:
+            _check(_mixed_lib.hpccg_hip_mixed_release(self.h), "mixed_release")
+
+    def mixed_workspace_bytes(self) -> int:
+        if _mixed_lib is None:
+            return 0
+        v = C.c_longlong(0)
+        _check(_mixed_lib.hpccg_hip_mixed_workspace_bytes(self.h, C.byref(v)), "mixed_workspace_bytes")
+        return v.value
+
     def close(self):
         # (a batch workspace goes with the matrix: the library's destroy hook,
         # whether or not the batch library was ever loaded)
@@ -584,6 +676,69 @@ def batch_live_workspaces() -> int:
         return 0
     c = C.c_int(0)
     _check(_batch_lib.hpccg_hip_batch_live_workspaces(C.byref(c)), "batch_live_workspaces")
+    return c.value
+
+
+
+# ---------------------------------------------------------------------------
+# mixed-precision solve (include/hpccg_hip_mixed.h)
+# ---------------------------------------------------------------------------
+def _one_column(a, what):
+    """A 1-D array or tensor as one column, shape (1, n): a view of the same
+    memory (X is updated in place), so it must have unit stride."""
+    if isinstance(a, int) or a.ndim != 1:
+        return a
+    stride = a.strides[0] // a.itemsize if isinstance(a, np.ndarray) else a.stride(0)
+    if a.shape[0] > 1 and stride != 1:
+        raise HPCCGError(f"{what}: a 1-D column must be contiguous (stride {stride})")
+    return a[None, :]
+
+
+def HPCCG_mixed(M: Matrix, B, X, max_iter: int = 500, tolerance: float = 0.0, max_sweeps: int = 8,
+                inner_rtol: float = -1.0, device=False, nrhs=None, ldb=None, ldx=None):
+    """nrhs CG solves against M with the matrix values streamed from an fp32
+    image, all arithmetic in fp64 (hpccg_hip_mixed_solve[_device]). Where the
+    image is exact (Matrix.mixed_info) column c is bitwise HPCCG(M, B[c], X[c]);
+    otherwise the solve is an iterative refinement against the fp64 matrix and
+    normr is the fp64 residual norm of the returned x. B, X: as HPCCG_batch (a
+    1-D array or tensor is one column). X is updated in place. Returns
+    (ierr, niters[nrhs], normr[nrhs], times)."""
+    L = mixed_lib()
+    B, X = _one_column(B, "B"), _one_column(X, "X")
+    bp, nb, ldb_ = _cols(B, nrhs, ldb, "B")
+    xp, nx_, ldx_ = _cols(X, nrhs, ldx, "X")
+    if nb != nx_:
+        raise HPCCGError(f"B holds {nb} columns, X {nx_}")
+    if not device and not (isinstance(B, np.ndarray) and isinstance(X, np.ndarray)):
+        raise HPCCGError("host solve: B and X are numpy arrays")
+    it = np.zeros(max(nb, 1), np.int32)
+    nr = np.zeros(max(nb, 1), np.float64)
+    times = np.zeros(7, np.float64)
+    f = L.hpccg_hip_mixed_solve_device if device else L.hpccg_hip_mixed_solve
+    rc = f(M.h, nb, bp, ldb_, xp, ldx_, max_iter, tolerance, int(max_sweeps), float(inner_rtol),
+           it.ctypes.data_as(C.POINTER(C.c_int)), nr.ctypes.data_as(C.POINTER(C.c_double)),
+           times.ctypes.data_as(C.POINTER(C.c_double)))
+    _check(rc, "HPCCG_mixed")
+    return rc, it[:nb], nr[:nb], times
+
+
+def HPC_sparsemv_mixed(M: Matrix, X, Y, nrhs=None, ldx=None, ldy=None) -> int:
+    """Y[c] = A~ X[c] for every column, A~ being the fp32 image of M (device
+    tensors / pointers, shape (nrhs, ld))."""
+    xp, nx_, ldx_ = _cols(X, nrhs, ldx, "X")
+    yp, ny_, ldy_ = _cols(Y, nrhs, ldy, "Y")
+    if nx_ != ny_:
+        raise HPCCGError(f"X holds {nx_} columns, Y {ny_}")
+    _check(mixed_lib().hpccg_hip_mixed_sparsemv(M.h, nx_, xp, ldx_, yp, ldy_), "HPC_sparsemv_mixed")
+    return 0
+
+
+def mixed_live_workspaces() -> int:
+    """Matrices that hold a mixed workspace (0 when the library was never loaded)."""
+    if _mixed_lib is None:
+        return 0
+    c = C.c_int(0)
+    _check(_mixed_lib.hpccg_hip_mixed_live_workspaces(C.byref(c)), "mixed_live_workspaces")
     return c.value
 
 

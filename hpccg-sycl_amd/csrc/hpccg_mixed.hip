@@ -1,0 +1,1258 @@
+// hpccg_mixed.hip -- mixed-precision CG (include/hpccg_hip_mixed.h,
+// lib/libhpccg_hip_mixed.so): kernels and host code of the third library.
+//
+// The solve is HBM-bound on the matrix values, so they are held a second time
+// in fp32 and streamed from there; every vector, every product and every sum is
+// fp64 (a value is widened in the register). Where every value survives the
+// round trip through float (exact) the fp32 image IS the matrix, and a column's
+// solve is bitwise hpccg_hip_solve_device of it. Otherwise the fp32 image is the
+// inner operator of an iterative refinement against the fp64 matrix.
+//
+// The fp32 image follows the image the matrix holds (SELL-512-A where it
+// exists, else SELL-512), slice by slice with the same slot-row bases, so the
+// offset tables / int32 columns are shared. Inside a slice the slots are
+// interleaved in pairs: slot pair (2q, 2q + 1) is [512 rows][2 slots] laid out
+// so that thread t (rows 2t, 2t + 1) reads one float4
+//   { v[2q][2t], v[2q][2t + 1], v[2q + 1][2t], v[2q + 1][2t + 1] }
+// at (base + 2q) * 512 + 4t: the value stream is 16 B per lane. An odd width's
+// last slot is a plain [512 rows] run read 8 B per lane (one load in 14 at
+// width 27), so the image is exactly 4 B per slot and no padded slot exists.
+//
+//   convert   k_mixed_convert: fp64 image -> fp32 image, counts the values that
+//             do not survive the round trip and those outside fp32 range
+//   SpMM      k_mixed_spmm_a<kW, kR> | k_mixed_spmm_sell<kR>: the batch
+//             library's slot loops over the fp32 image, kR = 1, 2, 4 columns
+//   p update, update, finalize: the batch library's shapes (hpccg_batch.hip),
+//             with the loop test's tolerance and iteration limit per column
+//   residual  k_mixed_residual: r = b - A x from an fp64 A x with the r.r slice
+//             partials | x = x + d (refinement)
+// Every dot keeps the rounding shape of hpccg_device.h. Launches are eager on
+// the matrix's stream; every kCheckEvery iterations the host reads one word
+// (columns ended). No kernel here waits on another block.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cfloat>
+#include <chrono>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <vector>
+
+#include "../../include/hpccg_hip_mixed.h"
+#include "hpccg_device.h"
+#include "hpccg_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace hpccg {
+
+namespace {
+
+// Per-column scalar state of the running recurrence: set by the host before a
+// recurrence starts, advanced by k_mixed_finalize only.
+struct ColState {
+    double rtrans;     // r_{k-1}.r_{k-1} of the iteration k about to run (HPCCG.cpp: rtrans)
+    double oldrtrans;  // r_{k-2}.r_{k-2}
+    double pap;        // p_k.Ap_k
+    double alpha;      // rtrans / pap
+    double beta;       // rtrans / oldrtrans (0.0 for k = 1)
+    double tol;        // the loop test's tolerance of this column's recurrence
+    int k;             // the iteration about to run (0: the prologue)
+    int run;           // 1: iteration k runs; 0: the column is frozen
+    int niters;        // iterations done once the recurrence has ended
+    int max_iter;      // the loop test's iteration limit of this column's recurrence
+};
+
+enum Dot : int { kDotRR = 0, kDotPAP = 1 };
+
+struct MixedArgs {
+    int n, nslices, grid;
+    int nrhs;      // columns of the call
+    int c0;        // first column of this launch (it covers c0 .. c0 + kR - 1, those < nrhs)
+    int cap;       // columns the workspace holds (stride of the partials)
+    int ng;        // ceil(nslices / kGroup)
+    int force;     // 1: every column runs whatever its state (the plain SpMM)
+    int nt, a_width;
+    double* p;     // local row 0 of column 0; column c at p + c * pcs (a zeroed guard zone around each)
+    long long xsell;  // SELL-512 column 0 relative to local row 0
+    double* r;     // column c at r + c * vcs, as Ap, x, b, ox, ob
+    double* Ap;
+    double* x;     // the recurrence's unknown (exact: the caller's x; refinement: the correction d)
+    double* b;     // the recurrence's right-hand side (exact: the caller's b; refinement: r_s)
+    double* ox;    // the caller's x
+    double* ob;    // the caller's b
+    long long pcs, vcs;
+    double* partial;  // [2][cap][nslices] slice partials (r.r, then p.Ap)
+    double* gsum;     // [2][cap][ng] group sums (beyond the finalize block's LDS only)
+    double* tot;      // [cap] r.r totals of the residual step
+    ColState* st;     // [cap]
+    double* hist;     // [cap][hstride]: hist[c][k] = r_k.r_k
+    long long hstride;
+    int* ended;       // columns whose loop has ended
+    const float* img;  // the fp32 values (layout above)
+    const int* aoff;
+    const unsigned int* abase;
+    const unsigned int* slice_base;
+    const int* cols;
+};
+
+// Wave-uniform table loads through the scalar cache (tables no kernel writes).
+template <class T>
+__device__ __forceinline__ T sld(const T* p)
+{
+    return *(const __attribute__((address_space(4))) T*)(p);
+}
+
+typedef float f4v __attribute__((ext_vector_type(4)));
+typedef float f2v __attribute__((ext_vector_type(2)));
+
+template <bool kNT>
+__device__ __forceinline__ f4v ld_f4(const float* __restrict__ p)
+{
+    if constexpr (kNT)
+        return __builtin_nontemporal_load(reinterpret_cast<const f4v*>(p));
+    else
+        return *reinterpret_cast<const f4v*>(p);
+}
+
+template <bool kNT>
+__device__ __forceinline__ f2v ld_f2(const float* __restrict__ p)
+{
+    if constexpr (kNT)
+        return __builtin_nontemporal_load(reinterpret_cast<const f2v*>(p));
+    else
+        return *reinterpret_cast<const f2v*>(p);
+}
+
+template <int kR>
+__device__ __forceinline__ bool active_cols(const MixedArgs& a, bool (&act)[kR], bool& all)
+{
+    bool any = false;
+    all = true;
+#pragma unroll
+    for (int j = 0; j < kR; j++) {
+        const int c = a.c0 + j;
+        act[j] = c < a.nrhs && (a.force || a.st[c].run != 0);
+        any = any || act[j];
+        all = all && act[j];
+    }
+    return any;
+}
+
+__device__ __forceinline__ double* slice_partials(const MixedArgs& a, int which, int c)
+{
+    return a.partial + ((size_t)which * a.cap + c) * (size_t)a.nslices;
+}
+
+// ---------------------------------------------------------------------------
+// fp64 image -> fp32 image, one block per slice. width > 0: every slice has
+// that many slots (base s * width); else slice s holds base_tab[s] ..
+// base_tab[s + 1]. flags[0] counts the values with (double)(float)v != v,
+// flags[1] those outside fp32 range (image not finite, or nonzero below
+// FLT_MIN). Zero holes and padding slots are exact.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_mixed_convert(const double* __restrict__ vals,
+                                                          const unsigned int* __restrict__ base_tab, int width,
+                                                          float* __restrict__ img, unsigned long long* flags)
+{
+    const int s = blockIdx.x;
+    const int w = width > 0 ? width : (int)(base_tab[s + 1] - base_tab[s]);
+    const size_t vb = (width > 0 ? (size_t)s * width : (size_t)base_tab[s]) * kSliceRows;
+    const double* __restrict__ src = vals + vb + (size_t)threadIdx.x * kRpt;
+    float* __restrict__ dst = img + vb;
+    const int wp = w & ~1;  // slots in pairs
+    unsigned int inexact = 0, range = 0;
+    for (int j = 0; j < w; j++) {
+        const Rows v = ld(src + (size_t)j * kSliceRows);
+        f2v f;
+        f.x = (float)v.v[0];
+        f.y = (float)v.v[1];
+#pragma unroll
+        for (int i = 0; i < kRpt; i++) {
+            const float fi = i ? f.y : f.x;
+            if (!((double)fi == v.v[i])) inexact++;
+            if (!isfinite(fi) || (v.v[i] != 0.0 && fabs(v.v[i]) < (double)FLT_MIN)) range++;
+        }
+        float* q = j < wp ? dst + (size_t)(j & ~1) * kSliceRows + (size_t)threadIdx.x * 4 + (j & 1) * 2
+                          : dst + (size_t)j * kSliceRows + (size_t)threadIdx.x * 2;
+        *reinterpret_cast<f2v*>(q) = f;
+    }
+    if (inexact) atomicAdd(flags, (unsigned long long)inexact);
+    if (range) atomicAdd(flags + 1, (unsigned long long)range);
+}
+
+// ---------------------------------------------------------------------------
+// p = x + 0.0*x (prologue, HPCCG.cpp:347) | p = r + beta*p (k == 1 reads r for
+// p, beta 0.0), per running column (k_batch_p's expressions).
+// ---------------------------------------------------------------------------
+template <int kR>
+__global__ __launch_bounds__(kBlock) void k_mixed_p(MixedArgs a, bool prologue)
+{
+    const int s = xcd_slice(a.grid);
+    if (s >= a.nslices) return;
+    const int row = s * kSliceRows + threadIdx.x * kRpt;
+#pragma unroll
+    for (int j = 0; j < kR; j++) {
+        const int c = a.c0 + j;
+        if (c >= a.nrhs) break;
+        if (!a.st[c].run) continue;  // (block-uniform)
+        double* __restrict__ pc = a.p + (size_t)c * a.pcs;
+        Rows o;
+        if (prologue) {
+            const Rows xv = ld(a.x + (size_t)c * a.vcs + row);
+#pragma unroll
+            for (int i = 0; i < kRpt; i++) o.v[i] = xv.v[i] + 0.0 * xv.v[i];
+        } else {
+            const int k = a.st[c].k;
+            const double beta = a.st[c].beta;
+            const Rows rv = ld(a.r + (size_t)c * a.vcs + row);
+            const Rows yv = (k == 1) ? rv : ld(pc + row);
+#pragma unroll
+            for (int i = 0; i < kRpt; i++) o.v[i] = rv.v[i] + beta * yv.v[i];
+        }
+        st_rows(pc, row, a.n, o);
+    }
+}
+
+// The SpMM epilogue of one column's two rows: store Ap; the rows' p.Ap terms
+// in spmv_rows_out's order, the slice partial by block_sum (the batch
+// library's spmm_rows_out).
+template <int kR>
+__device__ __forceinline__ void spmm_rows_out(const MixedArgs& a, bool prologue, int s, int row, const bool (&act)[kR],
+                                              const double (&sum)[kR][kRpt])
+{
+#pragma unroll
+    for (int j = 0; j < kR; j++) {
+        if (!act[j]) continue;  // (block-uniform)
+        const int c = a.c0 + j;
+        st_rows(a.Ap + (size_t)c * a.vcs, row, a.n, Rows{{sum[j][0], sum[j][1]}});
+        if (prologue) continue;  // HPCCG.cpp:351: the prologue SpMV has no p.Ap
+        const Rows pv = ld(a.p + (size_t)c * a.pcs + row);
+        double d = 0.0;
+#pragma unroll
+        for (int i = 0; i < kRpt; i++)
+            if (row + i < a.n) d += pv.v[i] * sum[j][i];
+        const double bs = block_sum<kBlock>(d);
+        if (threadIdx.x == 0) slice_partials(a, kDotPAP, c)[s] = bs;
+        __syncthreads();  // block_sum's LDS words are free for the next column
+    }
+}
+
+// One slot of the A image for every column: sum[c][i] = sum[c][i] +
+// (double)v[i] * x_c[row + off + i], the fp64 kernels' row-sum step.
+template <int kR, bool kAll>
+__device__ __forceinline__ void slot_a(const MixedArgs& a, float v0, float v1, int oj, const double* __restrict__ xr,
+                                       const bool (&act)[kR], double (&sum)[kR][kRpt])
+{
+    const double w0 = (double)v0, w1 = (double)v1;
+#pragma unroll
+    for (int c = 0; c < kR; c++) {
+        if (kAll || act[c]) {
+            const Rows xv = ld_u(xr + ((long long)c * a.pcs + oj));
+            sum[c][0] = sum[c][0] + w0 * xv.v[0];
+            sum[c][1] = sum[c][1] + w1 * xv.v[1];
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// SpMM over the fp32 SELL-512-A image: k_batch_spmm_a's slot loop, two slots
+// per 16-B value load. Column c's x is p_c at the slice's offsets (holes: 0.0
+// times a finite word of p_c's zeroed guard zone or a real neighbour). Per row
+// and column the products are added in slot order with no contraction: the
+// fp64 kernels' row sum of the widened values.
+// ---------------------------------------------------------------------------
+template <int kW, int kR, bool kNT, bool kAll>
+__device__ __forceinline__ void spmm_a_slots(const MixedArgs& a, const float* __restrict__ base,
+                                             const int* __restrict__ off, int wdt, const double* __restrict__ xr,
+                                             const bool (&act)[kR], double (&sum)[kR][kRpt])
+{
+    const float* __restrict__ vp = base + (size_t)threadIdx.x * 4;
+    const int np = wdt >> 1;
+#pragma unroll kW > 0 ? kW / 2 : 2
+    for (int q = 0; q < np; q++) {
+        const f4v v = ld_f4<kNT>(vp + (size_t)(2 * q) * kSliceRows);
+        const int o0 = sld(off + 2 * q), o1 = sld(off + 2 * q + 1);
+        slot_a<kR, kAll>(a, v.x, v.y, o0, xr, act, sum);
+        slot_a<kR, kAll>(a, v.z, v.w, o1, xr, act, sum);
+    }
+    if (wdt & 1) {  // (block-uniform) the odd width's last slot
+        const f2v v = ld_f2<kNT>(base + (size_t)(wdt - 1) * kSliceRows + (size_t)threadIdx.x * 2);
+        slot_a<kR, kAll>(a, v.x, v.y, sld(off + wdt - 1), xr, act, sum);
+    }
+}
+
+// kNT: the value loads are non-temporal. A template parameter of the kernel,
+// chosen on the host from the view's nt flag: as a branch inside the kernel
+// the two arms differ in the hint alone, the optimiser merges them and the
+// hint is lost (so it was with one column, where no other arm keeps them apart).
+// amdgpu_waves_per_eu(4): the register budget (at most 128 VGPRs; the batch
+// library's default), not a tuned target.
+template <int kW, bool kNT, int kR>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) void k_mixed_spmm_a(MixedArgs a,
+                                                                                                bool prologue)
+{
+    const int s = xcd_slice(a.grid);
+    if (s >= a.nslices) return;
+    bool act[kR], all;
+    if (!active_cols<kR>(a, act, all)) return;
+    const int wdt = kW > 0 ? kW : (int)(sld(a.abase + s + 1) - sld(a.abase + s));
+    const size_t vb = kW > 0 ? (size_t)s * kW : (size_t)sld(a.abase + s);
+    const float* __restrict__ base = a.img + vb * kSliceRows;
+    const int* __restrict__ off = a.aoff + (size_t)s * kAMax;
+    const int row = s * kSliceRows + threadIdx.x * kRpt;
+    const double* __restrict__ xr = a.p + (size_t)a.c0 * a.pcs + row;  // column c0 + c: x of column row + off at xr[c * pcs + off]
+    double sum[kR][kRpt];
+#pragma unroll
+    for (int c = 0; c < kR; c++)
+#pragma unroll
+        for (int i = 0; i < kRpt; i++) sum[c][i] = 0.0;
+    if (all)
+        spmm_a_slots<kW, kR, kNT, true>(a, base, off, wdt, xr, act, sum);
+    else
+        spmm_a_slots<kW, kR, kNT, false>(a, base, off, wdt, xr, act, sum);
+    spmm_rows_out<kR>(a, prologue, s, row, act, sum);
+}
+
+// One slot of the SELL-512 image for every column (k_batch_spmm_sell's step).
+template <int kR>
+__device__ __forceinline__ void slot_sell(const MixedArgs& a, float v0, float v1, int c0, int c1,
+                                          const double* __restrict__ x0, const bool (&act)[kR],
+                                          double (&sum)[kR][kRpt])
+{
+    const double w[kRpt] = {(double)v0, (double)v1};
+    const int col[kRpt] = {c0, c1};
+#pragma unroll
+    for (int c = 0; c < kR; c++) {
+        if (!act[c]) continue;  // (block-uniform)
+        const double* __restrict__ x = x0 + (size_t)c * a.pcs;
+#pragma unroll
+        for (int i = 0; i < kRpt; i++) {
+            const double xv = (col[i] >= 0) ? x[col[i]] : 0.0;
+            sum[c][i] = sum[c][i] + w[i] * xv;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// SpMM over the fp32 SELL-512 image (the shared int32 columns; matrices
+// without an A image): k_batch_spmm_sell's loop. Padding slots (column -1,
+// value 0) add +0.
+// ---------------------------------------------------------------------------
+template <bool kNT, int kR>
+__global__ __launch_bounds__(kBlock) void k_mixed_spmm_sell(MixedArgs a, bool prologue)
+{
+    const int s = xcd_slice(a.grid);
+    if (s >= a.nslices) return;
+    bool act[kR], all;
+    if (!active_cols<kR>(a, act, all)) return;
+    const size_t sb = (size_t)sld(a.slice_base + s) * kSliceRows;
+    const int w = (int)(sld(a.slice_base + s + 1) - sld(a.slice_base + s));
+    const float* __restrict__ base = a.img + sb;
+    const int* __restrict__ cp = a.cols + sb + (size_t)threadIdx.x * kRpt;
+    const double* __restrict__ x0 = a.p + ((long long)a.c0 * a.pcs + a.xsell);
+    double sum[kR][kRpt];
+#pragma unroll
+    for (int c = 0; c < kR; c++)
+#pragma unroll
+        for (int i = 0; i < kRpt; i++) sum[c][i] = 0.0;
+    typedef int i2v __attribute__((ext_vector_type(2)));
+    const int np = w >> 1;
+#pragma unroll 2
+    for (int q = 0; q < np; q++) {
+        const f4v v = ld_f4<kNT>(base + (size_t)(2 * q) * kSliceRows + (size_t)threadIdx.x * 4);
+        const i2v ca = *reinterpret_cast<const i2v*>(cp + (size_t)(2 * q) * kSliceRows);
+        const i2v cb = *reinterpret_cast<const i2v*>(cp + (size_t)(2 * q + 1) * kSliceRows);
+        slot_sell<kR>(a, v.x, v.y, ca.x, ca.y, x0, act, sum);
+        slot_sell<kR>(a, v.z, v.w, cb.x, cb.y, x0, act, sum);
+    }
+    if (w & 1) {  // (block-uniform) the odd width's last slot
+        const f2v v = ld_f2<kNT>(base + (size_t)(w - 1) * kSliceRows + (size_t)threadIdx.x * 2);
+        const i2v ca = *reinterpret_cast<const i2v*>(cp + (size_t)(w - 1) * kSliceRows);
+        slot_sell<kR>(a, v.x, v.y, ca.x, ca.y, x0, act, sum);
+    }
+    const int row = s * kSliceRows + threadIdx.x * kRpt;
+    spmm_rows_out<kR>(a, prologue, s, row, act, sum);
+}
+
+// ---------------------------------------------------------------------------
+// prologue: r = b + (-1)*Ap                         (HPCCG.cpp:352)
+// loop:     x = x + alpha*p; r = r + (-alpha)*Ap    (HPCCG.cpp:382-384)
+// then the r.r slice partial, per running column (k_batch_update's expressions).
+// ---------------------------------------------------------------------------
+template <int kR>
+__global__ __launch_bounds__(kBlock) void k_mixed_update(MixedArgs a, bool prologue)
+{
+    const int s = xcd_slice(a.grid);
+    if (s >= a.nslices) return;
+    const int row = s * kSliceRows + threadIdx.x * kRpt;
+#pragma unroll
+    for (int j = 0; j < kR; j++) {
+        const int c = a.c0 + j;
+        if (c >= a.nrhs) break;
+        if (!a.st[c].run) continue;  // (block-uniform)
+        double* __restrict__ rc = a.r + (size_t)c * a.vcs;
+        const Rows apv = ld(a.Ap + (size_t)c * a.vcs + row);
+        Rows rn;
+        if (prologue) {
+            const Rows bv = ld(a.b + (size_t)c * a.vcs + row);
+#pragma unroll
+            for (int i = 0; i < kRpt; i++) rn.v[i] = bv.v[i] + (-1.0) * apv.v[i];
+        } else {
+            const double alpha = a.st[c].alpha;
+            const Rows rv = ld(rc + row);
+#pragma unroll
+            for (int i = 0; i < kRpt; i++) rn.v[i] = rv.v[i] + (-alpha) * apv.v[i];
+            double* __restrict__ xc = a.x + (size_t)c * a.vcs;
+            const Rows xv = ld(xc + row);
+            const Rows pv = ld(a.p + (size_t)c * a.pcs + row);
+            Rows xn;
+#pragma unroll
+            for (int i = 0; i < kRpt; i++) xn.v[i] = xv.v[i] + alpha * pv.v[i];
+            st_rows(xc, row, a.n, xn);
+        }
+        st_rows(rc, row, a.n, rn);
+        double d = 0.0;
+#pragma unroll
+        for (int i = 0; i < kRpt; i++)
+            if (row + i < a.n) d += rn.v[i] * rn.v[i];
+        const double bs = block_sum<kBlock>(d);
+        if (threadIdx.x == 0) slice_partials(a, kDotRR, c)[s] = bs;
+        __syncthreads();  // block_sum's LDS words are free for the next column
+    }
+}
+
+// ---------------------------------------------------------------------------
+// The refinement's fp64 steps, per column marked running:
+//   residual (correct 0): r_s = b + (-1.0)*(A x), A x in Ap from the fp64
+//            matrix; stored as the inner recurrence's right-hand side, with
+//            the r_s.r_s slice partials
+//   correct 1: x = x + d
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_mixed_residual(MixedArgs a, int correct)
+{
+    const int s = xcd_slice(a.grid);
+    if (s >= a.nslices) return;
+    const int row = s * kSliceRows + threadIdx.x * kRpt;
+    for (int c = 0; c < a.nrhs; c++) {
+        if (!a.st[c].run) continue;  // (block-uniform)
+        const size_t co = (size_t)c * a.vcs;
+        if (correct) {
+            const Rows xv = ld(a.ox + co + row);
+            const Rows dv = ld(a.x + co + row);
+            Rows xn;
+#pragma unroll
+            for (int i = 0; i < kRpt; i++) xn.v[i] = xv.v[i] + dv.v[i];
+            st_rows(a.ox + co, row, a.n, xn);
+            continue;
+        }
+        const Rows bv = ld(a.ob + co + row);
+        const Rows av = ld(a.Ap + co + row);
+        Rows rn;
+#pragma unroll
+        for (int i = 0; i < kRpt; i++) rn.v[i] = bv.v[i] + (-1.0) * av.v[i];
+        st_rows(a.b + co, row, a.n, rn);
+        double d = 0.0;
+#pragma unroll
+        for (int i = 0; i < kRpt; i++)
+            if (row + i < a.n) d += rn.v[i] * rn.v[i];
+        const double bs = block_sum<kBlock>(d);
+        if (threadIdx.x == 0) slice_partials(a, kDotRR, c)[s] = bs;
+        __syncthreads();  // block_sum's LDS words are free for the next column
+    }
+}
+
+// ---------------------------------------------------------------------------
+// One block per column: the dot's two upper levels (k_batch_finalize's shapes),
+// then the column's scalars with the column's own tolerance and limit.
+//   p.Ap: alpha = rtrans / p.Ap                       (HPCCG.cpp:381-382)
+//   r.r of iteration k: hist[k]; oldrtrans, rtrans, beta for iteration k + 1
+//         and its loop test k + 1 < max_iter && normr > tol, normr being the
+//         value iteration k computed, sqrt(r_{k-1}.r_{k-1}) (HPCCG.cpp:358;
+//         sqrt(r_0.r_0) for k + 1 = 1).
+// total_only (the refinement's residual step): the total is stored in tot[c]
+// and the state is left alone.
+// ---------------------------------------------------------------------------
+constexpr int kFinThreads = 1024;
+constexpr int kFinLds = 2048;  // group sums kept in LDS up to 128 K slices
+
+__device__ __forceinline__ void advance_column(const MixedArgs& a, ColState* st, int c, int which, double tot)
+{
+    if (which == kDotPAP) {
+        st->pap = tot;
+        st->alpha = st->rtrans / tot;
+        return;
+    }
+    const int k = st->k;
+    const double old = st->rtrans;  // r_{k-1}.r_{k-1} (k >= 1)
+    a.hist[(size_t)c * a.hstride + k] = tot;
+    st->oldrtrans = old;
+    st->rtrans = tot;
+    st->beta = (k == 0) ? 0.0 : tot / old;
+    st->k = k + 1;
+    const bool run = k + 1 < st->max_iter && sqrt(k == 0 ? tot : old) > st->tol;
+    if (!run) {
+        st->run = 0;
+        st->niters = k;
+        atomicAdd(a.ended, 1);
+    }
+}
+
+__global__ __launch_bounds__(kFinThreads) void k_mixed_finalize(MixedArgs a, int which, int total_only)
+{
+    __shared__ double gs[kFinLds];
+    const int c = blockIdx.x;
+    ColState* const st = a.st + c;
+    if (!st->run) return;  // (block-uniform) a frozen column keeps its state
+    const int ng = a.ng;
+    const bool in_lds = ng <= kFinLds;
+    const double* const sp = slice_partials(a, which, c);
+    double* const gp = a.gsum + ((size_t)which * a.cap + c) * (size_t)ng;
+    const int lane = threadIdx.x & (kWave - 1);
+    constexpr int kWaves = kFinThreads / kWave;
+    constexpr int kB = 4;  // groups per wave per round, their loads issued before the sums
+    for (int g0 = threadIdx.x / kWave; g0 < ng; g0 += kWaves * kB) {
+        double v[kB];
+#pragma unroll
+        for (int b = 0; b < kB; b++) {
+            const int g = g0 + b * kWaves;
+            const int i = g * kGroup + lane;
+            v[b] = (g < ng && i < a.nslices) ? sp[i] : 0.0;
+        }
+#pragma unroll
+        for (int b = 0; b < kB; b++) {
+            const int g = g0 + b * kWaves;
+            const double w = wave_sum(v[b]);
+            if (lane == 0 && g < ng) {
+                if (in_lds)
+                    gs[g] = w;
+                else
+                    gp[g] = w;
+            }
+        }
+    }
+    if (!in_lds) __threadfence_block();
+    __syncthreads();  // group sums written by this block
+    if (threadIdx.x >= kWave) return;
+    const double tot = in_lds ? top_sum_wave([&](int i) { return gs[i]; }, ng, lane)
+                              : top_sum_wave([gp](int i) { return gp[i]; }, ng, lane);
+    if (lane != 0) return;
+    if (total_only) {
+        a.tot[c] = tot;
+        return;
+    }
+    advance_column(a, st, c, which, tot);
+}
+
+// ---------------------------------------------------------------------------
+// host
+// ---------------------------------------------------------------------------
+int fail(int code, const char* fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return hpccg_hip_internal_set_error(code, buf);
+}
+
+#define HIP_TRY(expr)                                                                          \
+    do {                                                                                       \
+        hipError_t e_ = (expr);                                                                \
+        if (e_ != hipSuccess)                                                                  \
+            return fail(e_ == hipErrorOutOfMemory ? HPCCG_HIP_ENOMEM : HPCCG_HIP_EHIP,         \
+                        "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);   \
+    } while (0)
+
+#define TRY(expr)                     \
+    do {                              \
+        int rc_ = (expr);             \
+        if (rc_ != 0) return rc_;     \
+    } while (0)
+
+constexpr int kCheckEvery = 32;  // iterations between two reads of the "columns ended" word
+constexpr double kInnerRtolDefault = 0x1p-20;
+
+// What the last solve did on one column.
+struct ColRecord {
+    std::vector<double> trace;  // the inner recurrences' normr, sweep after sweep
+    std::vector<int> iters;     // it_s
+    std::vector<double> resid;  // rho_s, then the final residual
+};
+
+struct Workspace {
+    MatrixView v;
+    // the fp32 image
+    float* img = nullptr;
+    long long img_bytes = 0;
+    bool built = false;
+    long long inexact = 0, out_of_range = 0;
+    // the vectors
+    int cap = 0;  // columns
+    bool refine = false;  // ob, ox are buffers of their own
+    long long pcs = 0, vcs = 0;
+    double *pbuf = nullptr, *r = nullptr, *Ap = nullptr, *x = nullptr, *b = nullptr, *ox = nullptr, *ob = nullptr;
+    double *partial = nullptr, *gsum = nullptr, *tot = nullptr;
+    ColState* st = nullptr;
+    int* ended = nullptr;
+    double* hist = nullptr;
+    long long hstride = 0;
+    int* h_ended = nullptr;  // pinned
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    long long bytes = 0;  // of the vectors
+    std::vector<ColState> hst;
+    std::vector<ColRecord> rec;  // per column of the last solve
+};
+
+std::mutex g_mu;
+std::map<const hpccg_hip_matrix*, Workspace*> g_ws;
+
+void free_vectors(Workspace* w)
+{
+    if (w->v.stream) (void)hipStreamSynchronize(w->v.stream);
+    for (void* q : {(void*)w->pbuf, (void*)w->r, (void*)w->Ap, (void*)w->x, (void*)w->b, (void*)w->ox, (void*)w->ob,
+                    (void*)w->partial, (void*)w->gsum, (void*)w->tot, (void*)w->st, (void*)w->ended, (void*)w->hist})
+        if (q) (void)hipFree(q);
+    w->pbuf = w->r = w->Ap = w->x = w->b = w->ox = w->ob = w->partial = w->gsum = w->tot = w->hist = nullptr;
+    w->st = nullptr;
+    w->ended = nullptr;
+    w->cap = 0;
+    w->refine = false;
+    w->hstride = 0;
+    w->bytes = 0;
+}
+
+void drop_workspace(const hpccg_hip_matrix* M)
+{
+    Workspace* w = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        auto it = g_ws.find(M);
+        if (it == g_ws.end()) return;
+        w = it->second;
+        g_ws.erase(it);
+    }
+    (void)hipSetDevice(w->v.device);
+    free_vectors(w);
+    if (w->img) (void)hipFree(w->img);
+    if (w->h_ended) (void)hipHostFree(w->h_ended);
+    if (w->ev0) (void)hipEventDestroy(w->ev0);
+    if (w->ev1) (void)hipEventDestroy(w->ev1);
+    delete w;
+}
+
+// the destroy hook (ctx: the matrix, the workspace's key; a no-op once released)
+void on_matrix_destroy(void* ctx) { drop_workspace(static_cast<const hpccg_hip_matrix*>(ctx)); }
+
+Workspace* find_workspace(const hpccg_hip_matrix* M)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    auto it = g_ws.find(M);
+    return it == g_ws.end() ? nullptr : it->second;
+}
+
+// The matrix's workspace record (made on first use, with the destroy hook).
+int get_record(hpccg_hip_matrix* M, const MatrixView& v, Workspace** out)
+{
+    Workspace* w = find_workspace(M);
+    if (!w) {
+        w = new Workspace;
+        {
+            std::lock_guard<std::mutex> lk(g_mu);
+            g_ws[M] = w;
+        }
+        w->v = v;
+        const int rc = hpccg_hip_internal_on_destroy(M, on_matrix_destroy, M);
+        if (rc) {
+            drop_workspace(M);
+            return rc;
+        }
+    }
+    w->v = v;
+    *out = w;
+    return 0;
+}
+
+int out_of_range(const Workspace* w)
+{
+    return fail(HPCCG_HIP_EINVAL,
+                "mixed: the matrix is outside fp32 range (%lld stored values with no finite, normal fp32 image)",
+                w->out_of_range);
+}
+
+// The fp32 image, built once per matrix on the device from the image it holds.
+int ensure_image(Workspace* w)
+{
+    if (w->built) return w->out_of_range ? out_of_range(w) : 0;
+    const MatrixView& v = w->v;
+    hipStream_t s = v.stream;
+    HIP_TRY(hipSetDevice(v.device));
+    const double* vals = v.has_a ? v.aval : v.vals;
+    const unsigned int* tab = v.has_a ? v.abase : v.slice_base;
+    const int width = v.has_a ? v.a_width : 0;
+    long long slot_rows = (long long)v.nslices * width;
+    if (width <= 0) {
+        unsigned int last = 0;
+        HIP_TRY(hipMemcpyAsync(&last, tab + v.nslices, sizeof last, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        slot_rows = last;
+    }
+    const size_t bytes = sizeof(float) * (size_t)std::max<long long>(slot_rows, 1) * kSliceRows;
+    unsigned long long* flags = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w->img), bytes));
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&flags), 2 * sizeof *flags);
+    unsigned long long h[2] = {0, 0};
+    if (e == hipSuccess) e = hipMemsetAsync(flags, 0, 2 * sizeof *flags, s);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_mixed_convert, dim3(v.nslices), dim3(kBlock), 0, s, vals, tab, width, w->img, flags);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h, flags, sizeof h, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (flags) (void)hipFree(flags);
+    if (e != hipSuccess) {
+        (void)hipFree(w->img);
+        w->img = nullptr;
+        return fail(e == hipErrorOutOfMemory ? HPCCG_HIP_ENOMEM : HPCCG_HIP_EHIP, "mixed: building the fp32 image: %s",
+                    hipGetErrorString(e));
+    }
+    w->built = true;
+    w->inexact = (long long)h[0];
+    w->out_of_range = (long long)h[1];
+    w->img_bytes = (long long)bytes;
+    if (w->out_of_range) {  // never solved with: the image goes, the verdict stays
+        (void)hipFree(w->img);
+        w->img = nullptr;
+        w->img_bytes = 0;
+        return out_of_range(w);
+    }
+    return 0;
+}
+
+template <class T>
+int alloc_zero(Workspace* w, T** p, size_t count)
+{
+    const size_t bytes = sizeof(T) * std::max<size_t>(count, 1);
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), bytes));
+    HIP_TRY(hipMemsetAsync(*p, 0, bytes, w->v.stream));
+    w->bytes += (long long)bytes;
+    return 0;
+}
+
+// Room for ncols columns and a history of max_iter + 1 entries per column;
+// refine: the refinement's two further vectors per column.
+int ensure_vectors(Workspace* w, int ncols, int max_iter, bool refine)
+{
+    const MatrixView& v = w->v;
+    HIP_TRY(hipSetDevice(v.device));
+    if (!w->h_ended) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&w->h_ended), sizeof(int), hipHostMallocDefault));
+    if (!w->ev0) HIP_TRY(hipEventCreate(&w->ev0));
+    if (!w->ev1) HIP_TRY(hipEventCreate(&w->ev1));
+    const long long hneed = (long long)max_iter + 1;
+    if (ncols <= w->cap && hneed <= w->hstride && (w->refine || !refine)) return 0;
+    const int cap = std::max(ncols, w->cap);
+    const long long hstride = std::max(hneed, w->hstride);
+    refine = refine || w->refine;
+    free_vectors(w);
+    const size_t npad = (size_t)v.npad;
+    const size_t ng = (size_t)(v.nslices + kGroup - 1) / kGroup;
+    w->pcs = (long long)(npad + 2 * (size_t)v.guard_rows);  // a p column: [guard | rows (padded) | guard]
+    w->vcs = (long long)npad;
+    // zeroed: p's guard zones and the rows past n are read (holes, full-width
+    // loads) and never stored by a kernel
+    int rc = alloc_zero(w, &w->pbuf, (size_t)w->pcs * cap);
+    if (!rc) rc = alloc_zero(w, &w->r, npad * cap);
+    if (!rc) rc = alloc_zero(w, &w->Ap, npad * cap);
+    if (!rc) rc = alloc_zero(w, &w->ox, npad * cap);
+    if (!rc) rc = alloc_zero(w, &w->ob, npad * cap);
+    if (!rc && refine) rc = alloc_zero(w, &w->x, npad * cap);
+    if (!rc && refine) rc = alloc_zero(w, &w->b, npad * cap);
+    if (!rc) rc = alloc_zero(w, &w->partial, 2 * (size_t)cap * std::max(v.nslices, 1));
+    if (!rc) rc = alloc_zero(w, &w->gsum, 2 * (size_t)cap * std::max<size_t>(ng, 1));
+    if (!rc) rc = alloc_zero(w, &w->tot, (size_t)cap);
+    if (!rc) rc = alloc_zero(w, &w->st, (size_t)cap);
+    if (!rc) rc = alloc_zero(w, &w->ended, 1);
+    if (!rc) rc = alloc_zero(w, &w->hist, (size_t)cap * (size_t)hstride);
+    if (rc) {
+        free_vectors(w);
+        return rc;
+    }
+    w->cap = cap;
+    w->refine = refine;
+    w->hstride = hstride;
+    return 0;
+}
+
+// What the mixed library runs on: one rank, no halo.
+int check_matrix(hpccg_hip_matrix* M, MatrixView* v)
+{
+    TRY(hpccg_hip_internal_view(M, v));
+    if (v->in_group) return fail(HPCCG_HIP_EINVAL, "mixed: the matrix is a member of an in-process group (one rank only)");
+    if (v->nranks > 1) return fail(HPCCG_HIP_EINVAL, "mixed: the matrix belongs to a communicator of %d ranks (one rank only)", v->nranks);
+    if (v->ghost_lo || v->ghost_hi) return fail(HPCCG_HIP_EINVAL, "mixed: the matrix has halo rows (one rank only)");
+    if (!v->has_a && !v->has_sell) return fail(HPCCG_HIP_EINVAL, "mixed: the matrix holds no device image");
+    return 0;
+}
+
+// inner: the recurrence runs on the refinement's (r_s, d) instead of (b, x)
+MixedArgs make_args(const Workspace* w, int nrhs, bool inner)
+{
+    const MatrixView& v = w->v;
+    MixedArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.n = v.n;
+    a.nslices = v.nslices;
+    a.grid = v.grid;
+    a.nrhs = nrhs;
+    a.cap = w->cap;
+    a.ng = (v.nslices + kGroup - 1) / kGroup;
+    a.nt = v.nt && !std::getenv("HPCCG_MIXED_NO_NT");  // (diagnostics: the A/B of the non-temporal value loads)
+    a.a_width = v.a_width;
+    a.p = w->pbuf + v.guard_rows;
+    a.xsell = v.sell_col_base;
+    a.r = w->r;
+    a.Ap = w->Ap;
+    a.ox = w->ox;
+    a.ob = w->ob;
+    a.x = inner ? w->x : w->ox;
+    a.b = inner ? w->b : w->ob;
+    a.pcs = w->pcs;
+    a.vcs = w->vcs;
+    a.partial = w->partial;
+    a.gsum = w->gsum;
+    a.tot = w->tot;
+    a.st = w->st;
+    a.hist = w->hist;
+    a.hstride = w->hstride;
+    a.ended = w->ended;
+    a.img = w->img;
+    a.aoff = v.aoff;
+    a.abase = v.abase;
+    a.slice_base = v.slice_base;
+    a.cols = v.cols;
+    return a;
+}
+
+// Columns [c0, c0 + kR) per launch: fours, a remainder of three as a four with
+// one idle column (one pass over the matrix, not two), of two as a two, of one
+// as a one (the single column is the main use: its own instantiation).
+template <class F>
+void for_chunks(int nrhs, F f)
+{
+    int c0 = 0;
+    while (nrhs - c0 >= 3) {
+        f(c0, 4);
+        c0 += 4;
+    }
+    if (nrhs - c0 == 2) f(c0, 2);
+    if (nrhs - c0 == 1) f(c0, 1);
+}
+
+#define HPCCG_MIXED_R(KERNEL, ...)                                                         \
+    do {                                                                                   \
+        if (R == 4)                                                                        \
+            hipLaunchKernelGGL((KERNEL<__VA_ARGS__ 4>), g, b, 0, s, a, prologue);          \
+        else if (R == 2)                                                                   \
+            hipLaunchKernelGGL((KERNEL<__VA_ARGS__ 2>), g, b, 0, s, a, prologue);          \
+        else                                                                               \
+            hipLaunchKernelGGL((KERNEL<__VA_ARGS__ 1>), g, b, 0, s, a, prologue);          \
+    } while (0)
+
+void launch_spmm(const Workspace* w, MixedArgs a, bool prologue)
+{
+    const dim3 g(a.grid), b(kBlock);
+    hipStream_t s = w->v.stream;
+    for_chunks(a.nrhs, [&](int c0, int R) {
+        a.c0 = c0;
+#define HPCCG_MIXED_NT(KERNEL, ...)                      \
+    do {                                                \
+        if (a.nt)                                       \
+            HPCCG_MIXED_R(KERNEL, __VA_ARGS__ true, );  \
+        else                                            \
+            HPCCG_MIXED_R(KERNEL, __VA_ARGS__ false, ); \
+    } while (0)
+        if (!w->v.has_a)
+            HPCCG_MIXED_NT(k_mixed_spmm_sell, );
+        else if (a.a_width == 27)
+            HPCCG_MIXED_NT(k_mixed_spmm_a, 27, );
+        else if (a.a_width == 7)
+            HPCCG_MIXED_NT(k_mixed_spmm_a, 7, );
+        else
+            HPCCG_MIXED_NT(k_mixed_spmm_a, 0, );
+#undef HPCCG_MIXED_NT
+    });
+}
+
+void launch_p(const Workspace* w, MixedArgs a, bool prologue)
+{
+    const dim3 g(a.grid), b(kBlock);
+    hipStream_t s = w->v.stream;
+    for_chunks(a.nrhs, [&](int c0, int R) {
+        a.c0 = c0;
+        HPCCG_MIXED_R(k_mixed_p, );
+    });
+}
+
+void launch_update(const Workspace* w, MixedArgs a, bool prologue)
+{
+    const dim3 g(a.grid), b(kBlock);
+    hipStream_t s = w->v.stream;
+    for_chunks(a.nrhs, [&](int c0, int R) {
+        a.c0 = c0;
+        HPCCG_MIXED_R(k_mixed_update, );
+    });
+}
+#undef HPCCG_MIXED_R
+
+void launch_finalize(const Workspace* w, const MixedArgs& a, int which, int total_only = 0)
+{
+    hipLaunchKernelGGL(k_mixed_finalize, dim3(a.nrhs), dim3(kFinThreads), 0, w->v.stream, a, which, total_only);
+}
+
+// Columns between the caller's column-major array and the workspace (kind:
+// host or device on the caller's side), stream-ordered.
+int copy_cols(const Workspace* w, double* dst, long long ldd, const double* src, long long lds, int nrhs,
+              hipMemcpyKind kind)
+{
+    for (int c = 0; c < nrhs; c++)
+        HIP_TRY(hipMemcpyAsync(dst + (size_t)c * (size_t)ldd, src + (size_t)c * (size_t)lds,
+                               sizeof(double) * (size_t)w->v.n, kind, w->v.stream));
+    return 0;
+}
+
+// The columns' states for the next launches: column c runs (fresh, with its
+// tolerance and limit) where run[c]. (Every upload is followed by a host
+// synchronisation before hst changes again.)
+int set_states(Workspace* w, int nrhs, const std::vector<char>& run, const std::vector<double>& tol,
+               const std::vector<int>& max_iter)
+{
+    w->hst.assign(nrhs, ColState{});
+    for (int c = 0; c < nrhs; c++) {
+        w->hst[c].run = run[c] ? 1 : 0;
+        w->hst[c].tol = tol[c];
+        w->hst[c].max_iter = max_iter[c];
+    }
+    HIP_TRY(hipMemcpyAsync(w->st, w->hst.data(), sizeof(ColState) * nrhs, hipMemcpyHostToDevice, w->v.stream));
+    HIP_TRY(hipMemsetAsync(w->ended, 0, sizeof(int), w->v.stream));
+    return 0;
+}
+
+// One CG recurrence per column marked run in the states just set: on (b, x) of
+// a. it[c] and the trace appended to rec[c] for those columns.
+int run_cg(Workspace* w, const MixedArgs& a, const std::vector<char>& run, const std::vector<int>& max_iter,
+           std::vector<int>& it)
+{
+    hipStream_t s = w->v.stream;
+    const int nrhs = a.nrhs;
+    int nrun = 0, kmax = 1;
+    for (int c = 0; c < nrhs; c++)
+        if (run[c]) {
+            nrun++;
+            kmax = std::max(kmax, max_iter[c]);
+        }
+    launch_p(w, a, true);
+    launch_spmm(w, a, true);
+    launch_update(w, a, true);
+    launch_finalize(w, a, kDotRR);
+    HIP_TRY(hipGetLastError());
+    for (int k = 1; k < kmax; k++) {
+        launch_p(w, a, false);
+        launch_spmm(w, a, false);
+        launch_finalize(w, a, kDotPAP);
+        launch_update(w, a, false);
+        launch_finalize(w, a, kDotRR);
+        if (k % kCheckEvery == 0 && k + 1 < kmax) {
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(w->h_ended, w->ended, sizeof(int), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            if (*w->h_ended >= nrun) break;  // later launches would be no-ops for every column
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    std::vector<ColState> st(nrhs);
+    std::vector<double> hist((size_t)nrhs * (size_t)w->hstride);
+    HIP_TRY(hipMemcpyAsync(st.data(), w->st, sizeof(ColState) * nrhs, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(hist.data(), w->hist, sizeof(double) * hist.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int c = 0; c < nrhs; c++) {
+        if (!run[c]) continue;
+        // a column still running when the launches ran out did max_iter - 1 iterations
+        const int n = st[c].run ? st[c].k - 1 : st[c].niters;
+        const double* h = hist.data() + (size_t)c * (size_t)w->hstride;
+        // normr after iteration k is sqrt(r_{k-1}.r_{k-1}) (HPCCG.cpp:371): the single solve's trace
+        std::vector<double>& tr = w->rec[c].trace;
+        tr.push_back(std::sqrt(h[0]));
+        for (int k = 1; k <= n; k++) tr.push_back(std::sqrt(h[k - 1]));
+        it[c] = n;
+    }
+    return 0;
+}
+
+// The solve on the columns staged in the workspace's ob and ox.
+int run_solve(hpccg_hip_matrix* M, Workspace* w, int nrhs, int max_iter, double tol, int max_sweeps, double inner_rtol,
+              int* niters, double* normr)
+{
+    hipStream_t s = w->v.stream;
+    w->rec.assign(nrhs, {});
+    std::vector<char> live(nrhs, 1);
+    std::vector<double> tols(nrhs, tol);
+    std::vector<int> limit(nrhs, max_iter), it(nrhs, 0);
+    if (w->inexact == 0) {  // the fp32 image is the matrix: the solve itself
+        const MixedArgs a = make_args(w, nrhs, false);
+        TRY(set_states(w, nrhs, live, tols, limit));
+        TRY(run_cg(w, a, live, limit, it));
+        for (int c = 0; c < nrhs; c++) {
+            ColRecord& rc = w->rec[c];
+            niters[c] = it[c];
+            normr[c] = rc.trace[it[c]];
+            rc.iters = {it[c]};
+            rc.resid = {rc.trace[0], normr[c]};
+        }
+        return 0;
+    }
+    const MixedArgs a = make_args(w, nrhs, true);
+    std::vector<int> left(nrhs, max_iter - 1);
+    std::vector<double> rr(nrhs, 0.0);
+    for (int c = 0; c < nrhs; c++) niters[c] = 0;
+    for (int sweep = 0;; sweep++) {
+        // 1. r_s = b - A x_s against the fp64 matrix, rho_s
+        for (int c = 0; c < nrhs; c++)
+            if (live[c]) TRY(hpccg_hip_sparsemv(M, w->ox + (size_t)c * w->vcs, w->Ap + (size_t)c * w->vcs));
+        TRY(set_states(w, nrhs, live, tols, limit));
+        hipLaunchKernelGGL(k_mixed_residual, dim3(a.grid), dim3(kBlock), 0, s, a, 0);
+        launch_finalize(w, a, kDotRR, 1);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(rr.data(), w->tot, sizeof(double) * nrhs, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        // 2. the columns that stop here
+        bool any = false;
+        for (int c = 0; c < nrhs; c++) {
+            if (!live[c]) continue;
+            const double rho = std::sqrt(rr[c]);
+            w->rec[c].resid.push_back(rho);
+            normr[c] = rho;
+            if (rho <= tol || sweep == max_sweeps || left[c] == 0) {
+                live[c] = 0;
+                continue;
+            }
+            any = true;
+            tols[c] = std::max(tol, inner_rtol * rho);
+            limit[c] = left[c] + 1;
+            HIP_TRY(hipMemsetAsync(w->x + (size_t)c * w->vcs, 0, sizeof(double) * (size_t)w->vcs, s));
+        }
+        if (!any) return 0;
+        // 3. the recurrence on A~ d = r_s from d = 0
+        TRY(set_states(w, nrhs, live, tols, limit));
+        TRY(run_cg(w, a, live, limit, it));
+        // 4. x_{s+1} = x_s + d
+        TRY(set_states(w, nrhs, live, tols, limit));
+        hipLaunchKernelGGL(k_mixed_residual, dim3(a.grid), dim3(kBlock), 0, s, a, 1);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s));
+        for (int c = 0; c < nrhs; c++) {
+            if (!live[c]) continue;
+            w->rec[c].iters.push_back(it[c]);
+            left[c] -= it[c];
+            niters[c] += it[c];
+        }
+    }
+}
+
+// f() with the caller's current device put back afterwards
+template <class F>
+int keep_device(F f)
+{
+    int cur = 0;
+    HIP_TRY(hipGetDevice(&cur));
+    const int rc = f();
+    (void)hipSetDevice(cur);
+    return rc;
+}
+
+int solve_common(hpccg_hip_matrix* M, int nrhs, const double* B, long long ldb, double* X, long long ldx, int max_iter,
+                 double tol, int max_sweeps, double inner_rtol, int* niters, double* normr, double* times, bool host)
+{
+    if (!M || !B || !X || !niters || !normr) return fail(HPCCG_HIP_EINVAL, "mixed: NULL argument");
+    if (nrhs <= 0) return fail(HPCCG_HIP_EINVAL, "mixed: nrhs %d (at least 1)", nrhs);
+    if (max_iter < 0) return fail(HPCCG_HIP_EINVAL, "mixed: max_iter %d is negative", max_iter);
+    if (max_sweeps < 1) return fail(HPCCG_HIP_EINVAL, "mixed: max_sweeps %d (at least 1)", max_sweeps);
+    if (std::isnan(inner_rtol) || inner_rtol >= 1.0)
+        return fail(HPCCG_HIP_EINVAL, "mixed: inner_rtol %g (in [0, 1); negative: the default)", inner_rtol);
+    if (inner_rtol < 0.0) inner_rtol = kInnerRtolDefault;
+    MatrixView v;
+    TRY(check_matrix(M, &v));
+    if (ldb < v.n || ldx < v.n)
+        return fail(HPCCG_HIP_EINVAL, "mixed: leading dimensions %lld, %lld below the %d rows", ldb, ldx, v.n);
+    if (times) std::fill(times, times + 7, 0.0);
+    if (v.n == 0) {
+        for (int c = 0; c < nrhs; c++) {
+            niters[c] = 0;
+            normr[c] = 0.0;
+        }
+        return 0;
+    }
+    if (max_iter < 1) max_iter = 1;
+    return keep_device([&]() -> int {
+        Workspace* w = nullptr;
+        TRY(get_record(M, v, &w));
+        TRY(ensure_image(w));
+        TRY(ensure_vectors(w, nrhs, max_iter, w->inexact != 0));
+        const hipMemcpyKind in = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+        const hipMemcpyKind out = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        const auto t0 = std::chrono::steady_clock::now();
+        TRY(copy_cols(w, w->ob, w->vcs, B, ldb, nrhs, in));
+        TRY(copy_cols(w, w->ox, w->vcs, X, ldx, nrhs, in));
+        if (host) HIP_TRY(hipStreamSynchronize(v.stream));
+        const auto t1 = std::chrono::steady_clock::now();
+        HIP_TRY(hipEventRecord(w->ev0, v.stream));
+        TRY(run_solve(M, w, nrhs, max_iter, tol, max_sweeps, inner_rtol, niters, normr));
+        HIP_TRY(hipEventRecord(w->ev1, v.stream));
+        const auto t2 = std::chrono::steady_clock::now();
+        TRY(copy_cols(w, X, ldx, w->ox, w->vcs, nrhs, out));
+        HIP_TRY(hipStreamSynchronize(v.stream));
+        const auto t3 = std::chrono::steady_clock::now();
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, w->ev0, w->ev1));
+        if (times) {
+            times[0] = 1e-3 * ms;
+            if (host) times[6] = std::chrono::duration<double>((t1 - t0) + (t3 - t2)).count();
+        }
+        return 0;
+    });
+}
+
+const ColRecord* find_record(const hpccg_hip_matrix* M, int col, const char* what)
+{
+    const Workspace* w = find_workspace(M);
+    if (!w || col < 0 || col >= (int)w->rec.size()) {
+        fail(HPCCG_HIP_EINVAL, "mixed: no %s of column %d (the last mixed solve had %d)", what, col,
+             w ? (int)w->rec.size() : 0);
+        return nullptr;
+    }
+    return &w->rec[col];
+}
+
+}  // namespace
+
+}  // namespace hpccg
+
+using namespace hpccg;
+
+extern "C" {
+
+int hpccg_hip_mixed_abi_version(void) { return 1; }
+
+int hpccg_hip_mixed_solve_device(hpccg_hip_matrix* M, int nrhs, const double* B_dev, long long ldb, double* X_dev,
+                                 long long ldx, int max_iter, double tolerance, int max_sweeps, double inner_rtol,
+                                 int* niters, double* normr, double* times)
+{
+    return solve_common(M, nrhs, B_dev, ldb, X_dev, ldx, max_iter, tolerance, max_sweeps, inner_rtol, niters, normr,
+                        times, false);
+}
+
+int hpccg_hip_mixed_solve(hpccg_hip_matrix* M, int nrhs, const double* B, long long ldb, double* X, long long ldx,
+                          int max_iter, double tolerance, int max_sweeps, double inner_rtol, int* niters, double* normr,
+                          double* times)
+{
+    return solve_common(M, nrhs, B, ldb, X, ldx, max_iter, tolerance, max_sweeps, inner_rtol, niters, normr, times,
+                        true);
+}
+
+int hpccg_hip_mixed_sparsemv(hpccg_hip_matrix* M, int nrhs, const double* X_dev, long long ldx, double* Y_dev,
+                             long long ldy)
+{
+    if (!M || !X_dev || !Y_dev) return fail(HPCCG_HIP_EINVAL, "mixed: NULL argument");
+    if (nrhs <= 0) return fail(HPCCG_HIP_EINVAL, "mixed: nrhs %d (at least 1)", nrhs);
+    MatrixView v;
+    TRY(check_matrix(M, &v));
+    if (ldx < v.n || ldy < v.n)
+        return fail(HPCCG_HIP_EINVAL, "mixed: leading dimensions %lld, %lld below the %d rows", ldx, ldy, v.n);
+    if (v.n == 0) return 0;
+    return keep_device([&]() -> int {
+        Workspace* w = nullptr;
+        TRY(get_record(M, v, &w));
+        TRY(ensure_image(w));
+        TRY(ensure_vectors(w, nrhs, 1, false));
+        // x into the guarded p columns, Ap = A~ p, Ap out
+        MixedArgs a = make_args(w, nrhs, false);
+        a.force = 1;
+        TRY(copy_cols(w, a.p, w->pcs, X_dev, ldx, nrhs, hipMemcpyDeviceToDevice));
+        launch_spmm(w, a, true);
+        HIP_TRY(hipGetLastError());
+        TRY(copy_cols(w, Y_dev, ldy, w->Ap, w->vcs, nrhs, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipStreamSynchronize(v.stream));
+        return 0;
+    });
+}
+
+int hpccg_hip_mixed_info(hpccg_hip_matrix* M, long long out[4])
+{
+    if (!M || !out) return fail(HPCCG_HIP_EINVAL, "mixed: NULL argument");
+    MatrixView v;
+    TRY(check_matrix(M, &v));
+    out[0] = 1;
+    out[1] = out[2] = out[3] = 0;
+    if (v.n == 0) return 0;
+    return keep_device([&]() -> int {
+        Workspace* w = nullptr;
+        TRY(get_record(M, v, &w));
+        TRY(ensure_image(w));
+        out[0] = w->inexact == 0 ? 1 : 0;
+        out[1] = w->img_bytes;
+        out[2] = w->bytes;
+        out[3] = w->inexact;
+        return 0;
+    });
+}
+
+int hpccg_hip_mixed_last_trace(const hpccg_hip_matrix* M, int col, double* out, int cap)
+{
+    if (!M || !out) return fail(HPCCG_HIP_EINVAL, "mixed: NULL argument");
+    const ColRecord* r = find_record(M, col, "trace");
+    if (!r) return HPCCG_HIP_EINVAL;
+    const int n = std::min<int>(std::max(cap, 0), (int)r->trace.size());
+    for (int i = 0; i < n; i++) out[i] = r->trace[i];
+    return n;
+}
+
+int hpccg_hip_mixed_last_sweeps(const hpccg_hip_matrix* M, int col, int* iters, double* resid, int cap)
+{
+    if (!M || !iters || !resid) return fail(HPCCG_HIP_EINVAL, "mixed: NULL argument");
+    const ColRecord* r = find_record(M, col, "sweeps");
+    if (!r) return HPCCG_HIP_EINVAL;
+    cap = std::max(cap, 0);
+    for (int i = 0; i < std::min<int>(cap, (int)r->iters.size()); i++) iters[i] = r->iters[i];
+    for (int i = 0; i < std::min<int>(cap, (int)r->resid.size()); i++) resid[i] = r->resid[i];
+    return (int)r->iters.size();
+}
+
+int hpccg_hip_mixed_release(hpccg_hip_matrix* M)
+{
+    if (!M) return fail(HPCCG_HIP_EINVAL, "mixed: NULL argument");
+    drop_workspace(M);
+    return 0;
+}
+
+int hpccg_hip_mixed_workspace_bytes(const hpccg_hip_matrix* M, long long* bytes)
+{
+    if (!M || !bytes) return fail(HPCCG_HIP_EINVAL, "mixed: NULL argument");
+    const Workspace* w = find_workspace(M);
+    *bytes = w ? w->bytes + w->img_bytes : 0;
+    return 0;
+}
+
+int hpccg_hip_mixed_live_workspaces(int* count)
+{
+    if (!count) return fail(HPCCG_HIP_EINVAL, "mixed: NULL argument");
+    std::lock_guard<std::mutex> lk(g_mu);
+    *count = (int)g_ws.size();
+    return 0;
+}
+
+}  // extern "C"

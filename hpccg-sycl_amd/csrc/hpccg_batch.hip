@@ -21,30 +21,28 @@
 // ended) and stops launching when all have. A column that has ended is frozen:
 // its blocks skip its loads and stores (block-uniform branches). No kernel here
 // waits on another block.
+// The recurrence itself -- the column's state, the bodies of the p update, the
+// SpMM epilogue, the update and the finalize, the workspace registry and the
+// launch loop -- is hpccg_columns.h; this unit adds the fp64 SpMM loops, the
+// guarded p / r layout and the group.
 //
 // Over an in-process rank group (include/hpccg_hip_batch_group.h; the last part
 // of the host code): every member runs these kernels on its rows, the ghost
 // planes of every column's p are copied between the members' p columns after
-// k_batch_p, k_batch_finalize stores each member's local total only (local),
-// and k_batch_group_sum adds the totals in rank order and advances the column's
-// state on every member. Column c is bitwise hpccg_hip_group_solve of it.
+// k_batch_p, k_batch_finalize stores each member's local total only
+// (store_total), and k_batch_group_sum adds the totals in rank order and
+// advances the column's state on every member. Column c is bitwise
+// hpccg_hip_group_solve of it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <map>
-#include <mutex>
 #include <vector>
 
 #include "../../include/hpccg_hip_batch.h"
 #include "../../include/hpccg_hip_batch_group.h"
-#include "hpccg_device.h"
-#include "hpccg_internal.h"
+#include "hpccg_columns.h"
 
 #pragma clang fp contract(off)
 
@@ -52,151 +50,35 @@ namespace hpccg {
 
 namespace {
 
-// Per-column scalar state, advanced by k_batch_finalize only (a group member's:
-// by k_batch_group_sum only).
-struct ColState {
-    double rtrans;     // r_{k-1}.r_{k-1} of the iteration k about to run (HPCCG.cpp: rtrans)
-    double oldrtrans;  // r_{k-2}.r_{k-2}
-    double pap;        // p_k.Ap_k
-    double alpha;      // rtrans / pap
-    double beta;       // rtrans / oldrtrans (0.0 for k = 1)
-    int k;             // the iteration about to run (0: the prologue)
-    int run;           // 1: iteration k runs (the prologue always does)
-    int niters;        // iterations done once the column has ended
-    int pad;
-};
-
-enum Dot : int { kDotRR = 0, kDotPAP = 1 };
-
-struct BatchArgs {
-    int n, nslices, grid;
-    int nrhs;      // columns of the batch
-    int c0;        // first column of this launch (it covers c0 .. c0 + kR - 1, those < nrhs)
-    int cap;       // columns the workspace holds (stride of the partials)
-    int ng;        // ceil(nslices / kGroup)
-    int max_iter;
-    double tol;
-    int force;     // 1: every column runs whatever its state (the plain SpMM)
-    int nt, a_width;
-    int tri;       // width 27: slices whose offsets come in runs of three use the x-triple plan
-    double* p;    // local row 0 of column 0; column c at p + c * pcs (guard zones around each;
-                  // a group member: ghost_lo rows below row 0, ghost_hi rows from row n)
-    long long xsell;  // SELL-512 column 0 relative to local row 0 (a group member: -ghost_lo)
-    double* tot;      // [2][cap] a group member's local dot totals (k_batch_finalize, local)
-    double* r;
-    double* Ap;    // column c at Ap + c * vcs
-    double* x;
-    double* b;
-    long long pcs, vcs;
-    double* partial;  // [2][cap][nslices] slice partials (r.r, then p.Ap)
-    double* gsum;     // [2][cap][ng] group sums (beyond the finalize block's LDS only)
-    ColState* st;     // [cap]
-    double* hist;     // [cap][hstride]: hist[c][k] = r_k.r_k
-    long long hstride;
-    int* ended;       // columns whose loop has ended
+struct BatchArgs : ColArgs {
+    // (ColArgs' p and r: guard zones around each column; a group member:
+    // ghost_lo rows below row 0, ghost_hi rows from row n; xsell: -ghost_lo;
+    // tot: a group member's local dot totals)
+    int tri;  // width 27: slices whose offsets come in runs of three use the x-triple plan
     const double* aval;
-    const int* aoff;
-    const unsigned int* abase;
-    const unsigned int* slice_base;
-    const int* cols;
     const double* vals;
 };
 
-// Wave-uniform table loads through the scalar cache (tables no kernel writes).
-template <class T>
-__device__ __forceinline__ T sld(const T* p)
-{
-    return *(const __attribute__((address_space(4))) T*)(p);
-}
-
-template <int kR>
-__device__ __forceinline__ bool active_cols(const BatchArgs& a, bool (&act)[kR], bool& all)
-{
-    bool any = false;
-    all = true;
-#pragma unroll
-    for (int j = 0; j < kR; j++) {
-        const int c = a.c0 + j;
-        act[j] = c < a.nrhs && (a.force || a.st[c].run != 0);
-        any = any || act[j];
-        all = all && act[j];
-    }
-    return any;
-}
-
-__device__ __forceinline__ double* slice_partials(const BatchArgs& a, int which, int c)
-{
-    return a.partial + ((size_t)which * a.cap + c) * (size_t)a.nslices;
-}
-
-__global__ void k_batch_init(BatchArgs a)
+// Every column of the call runs, with the call's tolerance and limit.
+__global__ void k_batch_init(BatchArgs a, int max_iter, double tol)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c == 0) *a.ended = 0;
     if (c >= a.nrhs) return;
     ColState s;
     s.rtrans = s.oldrtrans = s.pap = s.alpha = s.beta = 0.0;
+    s.tol = tol;
     s.k = 0;
     s.run = 1;
     s.niters = 0;
-    s.pad = 0;
+    s.max_iter = max_iter;
     a.st[c] = s;
 }
 
-// ---------------------------------------------------------------------------
-// p = x + 0.0*x (prologue, HPCCG.cpp:347) | p = r + beta*p (k_p_update's
-// expression: k == 1 reads r for p, beta 0.0), per running column.
-// ---------------------------------------------------------------------------
 template <int kR>
 __global__ __launch_bounds__(kBlock) void k_batch_p(BatchArgs a, bool prologue)
 {
-    const int s = xcd_slice(a.grid);
-    if (s >= a.nslices) return;
-    const int row = s * kSliceRows + threadIdx.x * kRpt;
-#pragma unroll
-    for (int j = 0; j < kR; j++) {
-        const int c = a.c0 + j;
-        if (c >= a.nrhs) break;
-        double* __restrict__ pc = a.p + (size_t)c * a.pcs;
-        Rows o;
-        if (prologue) {
-            const Rows xv = ld(a.x + (size_t)c * a.vcs + row);
-#pragma unroll
-            for (int i = 0; i < kRpt; i++) o.v[i] = xv.v[i] + 0.0 * xv.v[i];
-        } else {
-            if (!a.st[c].run) continue;
-            const int k = a.st[c].k;
-            const double beta = a.st[c].beta;
-            const Rows rv = ld(a.r + (size_t)c * a.pcs + row);
-            const Rows yv = (k == 1) ? rv : ld(pc + row);
-#pragma unroll
-            for (int i = 0; i < kRpt; i++) o.v[i] = rv.v[i] + beta * yv.v[i];
-        }
-        st_rows(pc, row, a.n, o);
-    }
-}
-
-// The SpMM epilogue of one column's two rows: store Ap; the rows' p.Ap terms
-// in spmv_rows_out's order, the slice partial by block_sum.
-template <int kR>
-__device__ __forceinline__ void spmm_rows_out(const BatchArgs& a, bool prologue, int s, int row, const bool (&act)[kR],
-                                              const double (&sum)[kR][kRpt])
-{
-#pragma unroll
-    for (int j = 0; j < kR; j++) {
-        if (!act[j]) continue;  // (block-uniform)
-        const int c = a.c0 + j;
-        st_rows(a.Ap + (size_t)c * a.vcs, row, a.n, Rows{{sum[j][0], sum[j][1]}});
-        if (prologue) continue;  // HPCCG.cpp:351: the prologue SpMV has no p.Ap
-        const Rows pv = ld(a.p + (size_t)c * a.pcs + row);
-        double d = 0.0;
-#pragma unroll
-        for (int i = 0; i < kRpt; i++)
-            if (row + i < a.n) d += pv.v[i] * sum[j][i];
-        const double bs = block_sum<kBlock>(d);
-        if (threadIdx.x == 0) slice_partials(a, kDotPAP, c)[s] = bs;
-        __syncthreads();  // block_sum's LDS words are free for the next column
-    }
+    col_p<kR>(a, prologue);
 }
 
 // ---------------------------------------------------------------------------
@@ -368,136 +250,17 @@ __global__ __launch_bounds__(kBlock) void k_batch_spmm_sell(BatchArgs a, bool pr
     spmm_rows_out<kR>(a, prologue, s, row, act, sum);
 }
 
-// ---------------------------------------------------------------------------
-// prologue: r = b + (-1)*Ap                         (HPCCG.cpp:352)
-// loop:     x = x + alpha*p; r = r + (-alpha)*Ap    (HPCCG.cpp:382-384)
-// then the r.r slice partial (k_update's expressions), per running column.
-// ---------------------------------------------------------------------------
 template <int kR>
 __global__ __launch_bounds__(kBlock) void k_batch_update(BatchArgs a, bool prologue)
 {
-    const int s = xcd_slice(a.grid);
-    if (s >= a.nslices) return;
-    const int row = s * kSliceRows + threadIdx.x * kRpt;
-#pragma unroll
-    for (int j = 0; j < kR; j++) {
-        const int c = a.c0 + j;
-        if (c >= a.nrhs) break;
-        if (!prologue && !a.st[c].run) continue;  // (block-uniform)
-        double* __restrict__ rc = a.r + (size_t)c * a.pcs;
-        const Rows apv = ld(a.Ap + (size_t)c * a.vcs + row);
-        Rows rn;
-        if (prologue) {
-            const Rows bv = ld(a.b + (size_t)c * a.vcs + row);
-#pragma unroll
-            for (int i = 0; i < kRpt; i++) rn.v[i] = bv.v[i] + (-1.0) * apv.v[i];
-        } else {
-            const double alpha = a.st[c].alpha;
-            const Rows rv = ld(rc + row);
-#pragma unroll
-            for (int i = 0; i < kRpt; i++) rn.v[i] = rv.v[i] + (-alpha) * apv.v[i];
-            double* __restrict__ xc = a.x + (size_t)c * a.vcs;
-            const Rows xv = ld(xc + row);
-            const Rows pv = ld(a.p + (size_t)c * a.pcs + row);
-            Rows xn;
-#pragma unroll
-            for (int i = 0; i < kRpt; i++) xn.v[i] = xv.v[i] + alpha * pv.v[i];
-            st_rows(xc, row, a.n, xn);
-        }
-        st_rows(rc, row, a.n, rn);
-        double d = 0.0;
-#pragma unroll
-        for (int i = 0; i < kRpt; i++)
-            if (row + i < a.n) d += rn.v[i] * rn.v[i];
-        const double bs = block_sum<kBlock>(d);
-        if (threadIdx.x == 0) slice_partials(a, kDotRR, c)[s] = bs;
-        __syncthreads();  // block_sum's LDS words are free for the next column
-    }
+    col_update<kR>(a, prologue);
 }
 
-// ---------------------------------------------------------------------------
-// One block per column: the dot's two upper levels (finalize_groups' and
-// k_finalize's shapes: a 64-lane butterfly per group of 64 slice partials,
-// top_sum_wave over the group sums), then the column's scalars.
-//   p.Ap: alpha = rtrans / p.Ap                       (HPCCG.cpp:381-382)
-//   r.r of iteration k: hist[k]; oldrtrans, rtrans, beta for iteration k + 1
-//         and its loop test k + 1 < max_iter && normr > tol, normr being the
-//         value iteration k computed, sqrt(r_{k-1}.r_{k-1}) (HPCCG.cpp:358,
-//         as cg_run restates it; sqrt(r_0.r_0) for k + 1 = 1).
-// ---------------------------------------------------------------------------
-constexpr int kFinThreads = 1024;
-constexpr int kFinLds = 2048;  // group sums kept in LDS up to 128 K slices
-
-// The column's scalars once a dot's total is known (one lane).
-__device__ __forceinline__ void advance_column(const BatchArgs& a, ColState* st, int c, int which, double tot)
+// store_total (a member of an in-process group): the total is this member's
+// part of the dot and the state is left to k_batch_group_sum.
+__global__ __launch_bounds__(kFinThreads) void k_batch_finalize(BatchArgs a, int which, int store_total)
 {
-    if (which == kDotPAP) {
-        st->pap = tot;
-        st->alpha = st->rtrans / tot;
-        return;
-    }
-    const int k = st->k;
-    const double old = st->rtrans;  // r_{k-1}.r_{k-1} (k >= 1)
-    a.hist[(size_t)c * a.hstride + k] = tot;
-    st->oldrtrans = old;
-    st->rtrans = tot;
-    st->beta = (k == 0) ? 0.0 : tot / old;
-    st->k = k + 1;
-    const bool run = k + 1 < a.max_iter && sqrt(k == 0 ? tot : old) > a.tol;
-    if (!run) {
-        st->run = 0;
-        st->niters = k;
-        atomicAdd(a.ended, 1);
-    }
-}
-
-// local (a member of an in-process group): the total is this member's part of
-// the dot; it is stored in tot[which][c] and the state is left to
-// k_batch_group_sum.
-__global__ __launch_bounds__(kFinThreads) void k_batch_finalize(BatchArgs a, int which, int local)
-{
-    __shared__ double gs[kFinLds];
-    const int c = blockIdx.x;
-    ColState* const st = a.st + c;
-    if (!st->run) return;  // (block-uniform) a frozen column keeps its state
-    const int ng = a.ng;
-    const bool in_lds = ng <= kFinLds;
-    const double* const sp = slice_partials(a, which, c);
-    double* const gp = a.gsum + ((size_t)which * a.cap + c) * (size_t)ng;
-    const int lane = threadIdx.x & (kWave - 1);
-    constexpr int kWaves = kFinThreads / kWave;
-    constexpr int kB = 4;  // groups per wave per round, their loads issued before the sums
-    for (int g0 = threadIdx.x / kWave; g0 < ng; g0 += kWaves * kB) {
-        double v[kB];
-#pragma unroll
-        for (int b = 0; b < kB; b++) {
-            const int g = g0 + b * kWaves;
-            const int i = g * kGroup + lane;
-            v[b] = (g < ng && i < a.nslices) ? sp[i] : 0.0;
-        }
-#pragma unroll
-        for (int b = 0; b < kB; b++) {
-            const int g = g0 + b * kWaves;
-            const double w = wave_sum(v[b]);
-            if (lane == 0 && g < ng) {
-                if (in_lds)
-                    gs[g] = w;
-                else
-                    gp[g] = w;
-            }
-        }
-    }
-    if (!in_lds) __threadfence_block();
-    __syncthreads();  // group sums written by this block
-    if (threadIdx.x >= kWave) return;
-    const double tot = in_lds ? top_sum_wave([&](int i) { return gs[i]; }, ng, lane)
-                              : top_sum_wave([gp](int i) { return gp[i]; }, ng, lane);
-    if (lane != 0) return;
-    if (local) {
-        a.tot[(size_t)which * a.cap + c] = tot;
-        return;
-    }
-    advance_column(a, st, c, which, tot);
+    col_finalize(a, which, store_total);
 }
 
 // ---------------------------------------------------------------------------
@@ -532,171 +295,51 @@ __global__ void k_batch_group_sum(BatchArgs a, GroupTotals g, int which)
 // ---------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------
-int fail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return hpccg_hip_internal_set_error(code, buf);
-}
-
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return fail(e_ == hipErrorOutOfMemory ? HPCCG_HIP_ENOMEM : HPCCG_HIP_EHIP,         \
-                        "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);   \
-    } while (0)
-
-#define TRY(expr)                     \
-    do {                              \
-        int rc_ = (expr);             \
-        if (rc_ != 0) return rc_;     \
-    } while (0)
-
-constexpr int kCheckEvery = 32;  // iterations between two reads of the "columns ended" word
-
-struct Workspace {
-    MatrixView v;
-    int cap = 0;  // columns
-    long long pcs = 0, vcs = 0;
-    double *pbuf = nullptr, *rbuf = nullptr, *Ap = nullptr, *x = nullptr, *b = nullptr;
-    double *partial = nullptr, *gsum = nullptr;
-    long long p0 = 0;       // local row 0 inside a p / r column (guard zone + the padded ghost_lo rows)
-    double* tot = nullptr;  // [2][cap] local dot totals (a group member)
+struct Workspace : ColWorkspace {
+    double *rbuf = nullptr, *x = nullptr, *b = nullptr;  // (r is guarded like p: stride pcs)
+    long long p0 = 0;  // local row 0 inside a p / r column (guard zone + the padded ghost_lo rows)
     hipEvent_t evr = nullptr, evs = nullptr;  // group: this member's stream is ready | member 0: the sum is done
-    ColState* st = nullptr;
-    int* ended = nullptr;
-    double* hist = nullptr;
-    long long hstride = 0;
-    int* h_ended = nullptr;  // pinned
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    long long bytes = 0;
-    std::vector<std::vector<double>> trace;  // per column of the last batch solve
-};
+    std::vector<std::vector<double>> trace;   // per column of the last batch solve
 
-std::mutex g_mu;
-std::map<const hpccg_hip_matrix*, Workspace*> g_ws;
-
-void free_device(Workspace* w)
-{
-    if (w->v.stream) (void)hipStreamSynchronize(w->v.stream);
-    for (void* q : {(void*)w->pbuf, (void*)w->rbuf, (void*)w->Ap, (void*)w->x, (void*)w->b, (void*)w->partial,
-                    (void*)w->gsum, (void*)w->st, (void*)w->ended, (void*)w->hist, (void*)w->tot})
-        if (q) (void)hipFree(q);
-    w->pbuf = w->rbuf = w->Ap = w->x = w->b = w->partial = w->gsum = w->hist = w->tot = nullptr;
-    w->st = nullptr;
-    w->ended = nullptr;
-    w->cap = 0;
-    w->hstride = 0;
-    w->bytes = 0;
-}
-
-void drop_workspace(const hpccg_hip_matrix* M)
-{
-    Workspace* w = nullptr;
+    void free_own_vectors()
     {
-        std::lock_guard<std::mutex> lk(g_mu);
-        auto it = g_ws.find(M);
-        if (it == g_ws.end()) return;
-        w = it->second;
-        g_ws.erase(it);
+        for (double* q : {rbuf, x, b})
+            if (q) (void)hipFree(q);
+        rbuf = x = b = nullptr;
     }
-    (void)hipSetDevice(w->v.device);
-    free_device(w);
-    if (w->h_ended) (void)hipHostFree(w->h_ended);
-    if (w->ev0) (void)hipEventDestroy(w->ev0);
-    if (w->ev1) (void)hipEventDestroy(w->ev1);
-    if (w->evr) (void)hipEventDestroy(w->evr);
-    if (w->evs) (void)hipEventDestroy(w->evs);
-    delete w;
-}
-
-// the destroy hook (ctx: the matrix, the workspace's key; a no-op once released)
-void on_matrix_destroy(void* ctx) { drop_workspace(static_cast<const hpccg_hip_matrix*>(ctx)); }
-
-Workspace* find_workspace(const hpccg_hip_matrix* M)
-{
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto it = g_ws.find(M);
-    return it == g_ws.end() ? nullptr : it->second;
-}
-
-template <class T>
-int alloc_zero(Workspace* w, T** p, size_t count)
-{
-    const size_t bytes = sizeof(T) * std::max<size_t>(count, 1);
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), bytes));
-    HIP_TRY(hipMemsetAsync(*p, 0, bytes, w->v.stream));
-    w->bytes += (long long)bytes;
-    return 0;
-}
+    void free_own_rest()
+    {
+        if (evr) (void)hipEventDestroy(evr);
+        if (evs) (void)hipEventDestroy(evs);
+    }
+};
 
 // The matrix's workspace record with room for nrhs columns (ncols 0: the record
 // only) and a history of max_iter + 1 entries per column.
 int get_workspace(hpccg_hip_matrix* M, const MatrixView& v, int ncols, int max_iter, Workspace** out)
 {
-    Workspace* w = find_workspace(M);
-    if (!w) {
-        w = new Workspace;
-        {
-            std::lock_guard<std::mutex> lk(g_mu);
-            g_ws[M] = w;
-        }
-        w->v = v;
-        const int rc = hpccg_hip_internal_on_destroy(M, on_matrix_destroy, M);
-        if (rc) {
-            drop_workspace(M);
-            return rc;
-        }
-    }
-    w->v = v;
-    *out = w;
+    TRY(g_ws<Workspace>.record(M, v, out));
     if (ncols <= 0) return 0;
-    HIP_TRY(hipSetDevice(v.device));
-    if (!w->h_ended) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&w->h_ended), sizeof(int), hipHostMallocDefault));
-    if (!w->ev0) HIP_TRY(hipEventCreate(&w->ev0));
-    if (!w->ev1) HIP_TRY(hipEventCreate(&w->ev1));
-    if (v.in_group && !w->evr) HIP_TRY(hipEventCreateWithFlags(&w->evr, hipEventDisableTiming));
-    if (v.in_group && !w->evs) HIP_TRY(hipEventCreateWithFlags(&w->evs, hipEventDisableTiming));
-    const long long hneed = (long long)max_iter + 1;
-    if (ncols <= w->cap && hneed <= w->hstride) return 0;
-    const int cap = std::max(ncols, w->cap);
-    const long long hstride = std::max(hneed, w->hstride);
-    free_device(w);
+    Workspace* w = *out;
     const size_t npad = (size_t)v.npad;
-    const size_t ng = (size_t)(v.nslices + kGroup - 1) / kGroup;
     // a p column: [guard | ghost_lo (padded) | local rows (padded) | ghost_hi's spill (padded) | guard].
     // The ghost_hi rows start at local row n (where the single solve's p has
     // them): inside the last slice's padding rows and, past npad, in ghi_pad.
     // glo_pad is whole slices, so local row 0 keeps the buffer's alignment.
     const size_t glo_pad = ((size_t)v.ghost_lo + kSliceRows - 1) / kSliceRows * kSliceRows;
     const size_t ghi_pad = v.ghost_hi ? ((size_t)v.ghost_hi + 2 + kSliceRows - 1) / kSliceRows * kSliceRows : 0;
-    w->p0 = (long long)((size_t)v.guard_rows + glo_pad);
-    w->pcs = (long long)(npad + glo_pad + ghi_pad + 2 * (size_t)v.guard_rows);
-    w->vcs = (long long)npad;
-    // zeroed: the guard zones and the rows past n of p and r are read (holes,
-    // full-width loads) and never stored by a kernel (p's ghost rows: by the
-    // group's halo copies only)
-    int rc = alloc_zero(w, &w->pbuf, (size_t)w->pcs * cap);
-    if (!rc) rc = alloc_zero(w, &w->rbuf, (size_t)w->pcs * cap);
-    if (!rc) rc = alloc_zero(w, &w->Ap, npad * cap);
-    if (!rc) rc = alloc_zero(w, &w->x, npad * cap);
-    if (!rc) rc = alloc_zero(w, &w->b, npad * cap);
-    if (!rc) rc = alloc_zero(w, &w->partial, 2 * (size_t)cap * std::max(v.nslices, 1));
-    if (!rc) rc = alloc_zero(w, &w->gsum, 2 * (size_t)cap * std::max<size_t>(ng, 1));
-    if (!rc) rc = alloc_zero(w, &w->st, (size_t)cap);
-    if (!rc && v.in_group) rc = alloc_zero(w, &w->tot, 2 * (size_t)cap);
-    if (!rc) rc = alloc_zero(w, &w->ended, 1);
-    if (!rc) rc = alloc_zero(w, &w->hist, (size_t)cap * (size_t)hstride);
-    if (rc) {
-        free_device(w);
-        return rc;
-    }
-    w->cap = cap;
-    w->hstride = hstride;
+    const long long pcs = (long long)(npad + glo_pad + ghi_pad + 2 * (size_t)v.guard_rows);
+    // (r's guard zones and rows past n are read and never stored, as p's; p's
+    // ghost rows are stored by the group's halo copies only)
+    TRY(ensure_columns(w, ncols, max_iter, true, pcs, v.in_group ? 2 : 0, [&](int cap) {
+        w->p0 = (long long)((size_t)v.guard_rows + glo_pad);
+        TRY(alloc_zero(w, &w->rbuf, (size_t)pcs * cap));
+        TRY(alloc_zero(w, &w->x, npad * cap));
+        TRY(alloc_zero(w, &w->b, npad * cap));
+        return 0;
+    }));
+    if (v.in_group && !w->evr) HIP_TRY(hipEventCreateWithFlags(&w->evr, hipEventDisableTiming));
+    if (v.in_group && !w->evs) HIP_TRY(hipEventCreateWithFlags(&w->evs, hipEventDisableTiming));
     return 0;
 }
 
@@ -712,64 +355,27 @@ int check_matrix(hpccg_hip_matrix* M, MatrixView* v, bool group1 = false)
     return 0;
 }
 
-BatchArgs make_args(const Workspace* w, int nrhs, int max_iter, double tol)
+BatchArgs make_args(const Workspace* w, int nrhs)
 {
     const MatrixView& v = w->v;
-    BatchArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.n = v.n;
-    a.nslices = v.nslices;
-    a.grid = v.grid;
-    a.nrhs = nrhs;
-    a.cap = w->cap;
-    a.ng = (v.nslices + kGroup - 1) / kGroup;
-    a.max_iter = max_iter;
-    a.tol = tol;
-    a.nt = v.nt;
-    a.a_width = v.a_width;
+    BatchArgs a{};
+    fill_args(&a, w, nrhs);
     a.tri = std::getenv("HPCCG_BATCH_NO_TRIPLES") ? 0 : 1;  // diagnostics: A/B of the x-triple plan
     a.p = w->pbuf + w->p0;
     a.r = w->rbuf + w->p0;
-    a.xsell = v.sell_col_base;
-    a.tot = w->tot;
-    a.Ap = w->Ap;
+    a.rcs = w->pcs;
     a.x = w->x;
     a.b = w->b;
-    a.pcs = w->pcs;
-    a.vcs = w->vcs;
-    a.partial = w->partial;
-    a.gsum = w->gsum;
-    a.st = w->st;
-    a.hist = w->hist;
-    a.hstride = w->hstride;
-    a.ended = w->ended;
     a.aval = v.aval;
-    a.aoff = v.aoff;
-    a.abase = v.abase;
-    a.slice_base = v.slice_base;
-    a.cols = v.cols;
     a.vals = v.vals;
     return a;
-}
-
-// Columns [c0, c0 + kR) per launch: fours, a remainder of three as a four with
-// one idle column (one pass over the matrix, not two), of one or two as a two.
-template <class F>
-void for_chunks(int nrhs, F f)
-{
-    int c0 = 0;
-    while (nrhs - c0 >= 3) {
-        f(c0, 4);
-        c0 += 4;
-    }
-    if (c0 < nrhs) f(c0, 2);
 }
 
 void launch_spmm(const Workspace* w, BatchArgs a, bool prologue)
 {
     const dim3 g(a.grid), b(kBlock);
     hipStream_t s = w->v.stream;
-    for_chunks(a.nrhs, [&](int c0, int R) {
+    for_chunks(a.nrhs, false, [&](int c0, int R) {
         a.c0 = c0;
         if (!w->v.has_a) {
             if (R == 4)
@@ -799,7 +405,7 @@ void launch_spmm(const Workspace* w, BatchArgs a, bool prologue)
 
 void launch_p(const Workspace* w, BatchArgs a, bool prologue)
 {
-    for_chunks(a.nrhs, [&](int c0, int R) {
+    for_chunks(a.nrhs, false, [&](int c0, int R) {
         a.c0 = c0;
         if (R == 4)
             hipLaunchKernelGGL(k_batch_p<4>, dim3(a.grid), dim3(kBlock), 0, w->v.stream, a, prologue);
@@ -810,7 +416,7 @@ void launch_p(const Workspace* w, BatchArgs a, bool prologue)
 
 void launch_update(const Workspace* w, BatchArgs a, bool prologue)
 {
-    for_chunks(a.nrhs, [&](int c0, int R) {
+    for_chunks(a.nrhs, false, [&](int c0, int R) {
         a.c0 = c0;
         if (R == 4)
             hipLaunchKernelGGL(k_batch_update<4>, dim3(a.grid), dim3(kBlock), 0, w->v.stream, a, prologue);
@@ -819,20 +425,9 @@ void launch_update(const Workspace* w, BatchArgs a, bool prologue)
     });
 }
 
-void launch_finalize(const Workspace* w, const BatchArgs& a, int which, int local = 0)
+void launch_finalize(const Workspace* w, const BatchArgs& a, int which, int store_total = 0)
 {
-    hipLaunchKernelGGL(k_batch_finalize, dim3(a.nrhs), dim3(kFinThreads), 0, w->v.stream, a, which, local);
-}
-
-// Columns between the caller's column-major array and the workspace (kind:
-// host or device on the caller's side), stream-ordered.
-int copy_cols(const Workspace* w, double* dst, long long ldd, const double* src, long long lds, int nrhs,
-              hipMemcpyKind kind)
-{
-    for (int c = 0; c < nrhs; c++)
-        HIP_TRY(hipMemcpyAsync(dst + (size_t)c * (size_t)ldd, src + (size_t)c * (size_t)lds,
-                               sizeof(double) * (size_t)w->v.n, kind, w->v.stream));
-    return 0;
+    hipLaunchKernelGGL(k_batch_finalize, dim3(a.nrhs), dim3(kFinThreads), 0, w->v.stream, a, which, store_total);
 }
 
 int read_results(Workspace* w, int nrhs, int* niters, double* normr, double* wall);
@@ -841,28 +436,10 @@ int read_results(Workspace* w, int nrhs, int* niters, double* normr, double* wal
 int run_cg(Workspace* w, int nrhs, int max_iter, double tol, int* niters, double* normr, double* wall)
 {
     hipStream_t s = w->v.stream;
-    const BatchArgs a = make_args(w, nrhs, max_iter, tol);
+    const BatchArgs a = make_args(w, nrhs);
     HIP_TRY(hipEventRecord(w->ev0, s));
-    hipLaunchKernelGGL(k_batch_init, dim3((nrhs + 63) / 64), dim3(64), 0, s, a);
-    launch_p(w, a, true);
-    launch_spmm(w, a, true);
-    launch_update(w, a, true);
-    launch_finalize(w, a, kDotRR);
-    HIP_TRY(hipGetLastError());
-    for (int k = 1; k < max_iter; k++) {
-        launch_p(w, a, false);
-        launch_spmm(w, a, false);
-        launch_finalize(w, a, kDotPAP);
-        launch_update(w, a, false);
-        launch_finalize(w, a, kDotRR);
-        if (k % kCheckEvery == 0 && k + 1 < max_iter) {
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(w->h_ended, w->ended, sizeof(int), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            if (*w->h_ended >= nrhs) break;  // later launches would be no-ops for every column
-        }
-    }
-    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_batch_init, dim3((nrhs + 63) / 64), dim3(64), 0, s, a, max_iter, tol);
+    TRY(run_recurrence(w, a, nrhs, max_iter, launch_p, launch_spmm, launch_update, launch_finalize));
     return read_results(w, nrhs, niters, normr, wall);
 }
 
@@ -870,28 +447,17 @@ int run_cg(Workspace* w, int nrhs, int max_iter, double tol, int* niters, double
 // followed every member's): its wall time, the columns' states and traces.
 int read_results(Workspace* w, int nrhs, int* niters, double* normr, double* wall)
 {
-    hipStream_t s = w->v.stream;
-    HIP_TRY(hipEventRecord(w->ev1, s));
-    std::vector<ColState> st(nrhs);
-    std::vector<double> hist((size_t)nrhs * (size_t)w->hstride);
-    HIP_TRY(hipMemcpyAsync(st.data(), w->st, sizeof(ColState) * nrhs, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(hist.data(), w->hist, sizeof(double) * hist.size(), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipEventRecord(w->ev1, w->v.stream));
+    std::vector<ColState> st;
+    std::vector<double> hist;
+    TRY(read_columns(w, nrhs, &st, &hist));
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, w->ev0, w->ev1));
     if (wall) *wall = 1e-3 * ms;
     w->trace.assign(nrhs, {});
     for (int c = 0; c < nrhs; c++) {
-        // a column still running when the launches ran out did max_iter - 1 iterations
-        const int it = st[c].run ? st[c].k - 1 : st[c].niters;
-        const double* h = hist.data() + (size_t)c * (size_t)w->hstride;
-        // normr after iteration k is sqrt(r_{k-1}.r_{k-1}) (HPCCG.cpp:371): the single solve's trace
-        std::vector<double>& tr = w->trace[c];
-        tr.assign(it + 1, 0.0);
-        tr[0] = std::sqrt(h[0]);
-        for (int k = 1; k <= it; k++) tr[k] = std::sqrt(h[k - 1]);
-        niters[c] = it;
-        normr[c] = tr[it];
+        niters[c] = column_trace(st[c], hist.data() + (size_t)c * (size_t)w->hstride, &w->trace[c]);
+        normr[c] = w->trace[c][niters[c]];
     }
     return 0;
 }
@@ -974,7 +540,7 @@ int sparsemv_one(hpccg_hip_matrix* M, int nrhs, const double* X_dev, long long l
     Workspace* w = nullptr;
     TRY(get_workspace(M, v, nrhs, 1, &w));
     // x into the guarded p columns, Ap = A p, Ap out
-    BatchArgs a = make_args(w, nrhs, 1, 0.0);
+    BatchArgs a = make_args(w, nrhs);
     a.force = 1;
     TRY(copy_cols(w, a.p, w->pcs, X_dev, ldx, nrhs, hipMemcpyDeviceToDevice));
     launch_spmm(w, a, true);
@@ -1045,13 +611,13 @@ int use(const Group& G, int r)
     return 0;
 }
 
-int group_workspaces(hpccg_hip_matrix* const* Ms, Group* G, int nrhs, int max_iter, double tol)
+int group_workspaces(hpccg_hip_matrix* const* Ms, Group* G, int nrhs, int max_iter)
 {
     G->w.assign(G->P, nullptr);
     G->a.resize(G->P);
     for (int r = 0; r < G->P; r++) {
         TRY(get_workspace(Ms[r], G->v[r], nrhs, max_iter, &G->w[r]));
-        G->a[r] = make_args(G->w[r], nrhs, max_iter, tol);
+        G->a[r] = make_args(G->w[r], nrhs);
     }
     return 0;
 }
@@ -1125,10 +691,9 @@ int group_sum(const Group& G, const GroupTotals& gt, int which, int nrhs)
 }
 
 // The batch CG over the group on the columns staged in the members' b and x.
-int group_run_cg(const Group& G, int nrhs, int max_iter, int* niters, double* normr, double* wall)
+int group_run_cg(const Group& G, int nrhs, int max_iter, double tol, int* niters, double* normr, double* wall)
 {
-    GroupTotals gt;
-    std::memset(&gt, 0, sizeof gt);
+    GroupTotals gt{};
     gt.nranks = G.P;
     for (int r = 0; r < G.P; r++) {
         gt.cap[r] = G.w[r]->cap;
@@ -1140,7 +705,7 @@ int group_run_cg(const Group& G, int nrhs, int max_iter, int* niters, double* no
     HIP_TRY(hipEventRecord(w0->ev0, G.v[0].stream));
     for (int r = 0; r < G.P; r++) {
         TRY(use(G, r));
-        hipLaunchKernelGGL(k_batch_init, dim3((nrhs + 63) / 64), dim3(64), 0, G.v[r].stream, G.a[r]);
+        hipLaunchKernelGGL(k_batch_init, dim3((nrhs + 63) / 64), dim3(64), 0, G.v[r].stream, G.a[r], max_iter, tol);
         launch_p(G.w[r], G.a[r], true);
     }
     TRY(group_halo(G, nrhs));
@@ -1208,14 +773,14 @@ int group_solve(hpccg_hip_matrix* const* Ms, const Group& G0, int nrhs, const do
         return 0;
     }
     if (max_iter < 1) max_iter = 1;
-    TRY(group_workspaces(Ms, &G, nrhs, max_iter, tol));
+    TRY(group_workspaces(Ms, &G, nrhs, max_iter));
     for (int r = 0; r < G.P; r++) {
         TRY(use(G, r));
         TRY(copy_cols(G.w[r], G.w[r]->b, G.w[r]->vcs, B[r], ldb[r], nrhs, hipMemcpyDeviceToDevice));
         TRY(copy_cols(G.w[r], G.w[r]->x, G.w[r]->vcs, X[r], ldx[r], nrhs, hipMemcpyDeviceToDevice));
     }
     double wall = 0.0;
-    TRY(group_run_cg(G, nrhs, max_iter, niters, normr, &wall));
+    TRY(group_run_cg(G, nrhs, max_iter, tol, niters, normr, &wall));
     for (int r = 0; r < G.P; r++) {
         TRY(use(G, r));
         TRY(copy_cols(G.w[r], X[r], ldx[r], G.w[r]->x, G.w[r]->vcs, nrhs, hipMemcpyDeviceToDevice));
@@ -1229,7 +794,7 @@ int group_sparsemv(hpccg_hip_matrix* const* Ms, const Group& G0, int nrhs, const
                    const long long* ldx, double* const* Y, const long long* ldy)
 {
     Group G = G0;
-    TRY(group_workspaces(Ms, &G, nrhs, 1, 0.0));
+    TRY(group_workspaces(Ms, &G, nrhs, 1));
     // x into the local rows of the p columns, their halo, Ap = A p, Ap out
     for (int r = 0; r < G.P; r++) {
         G.a[r].force = 1;
@@ -1250,17 +815,6 @@ int group_sparsemv(hpccg_hip_matrix* const* Ms, const Group& G0, int nrhs, const
         HIP_TRY(hipStreamSynchronize(G.v[r].stream));
     }
     return 0;
-}
-
-// f() with the caller's current device put back afterwards
-template <class F>
-int keep_device(F f)
-{
-    int cur = 0;
-    HIP_TRY(hipGetDevice(&cur));
-    const int rc = f();
-    (void)hipSetDevice(cur);
-    return rc;
 }
 
 int check_group_args(hpccg_hip_matrix* const* Ms, int nranks, int nrhs)
@@ -1298,7 +852,7 @@ int hpccg_hip_batch_solve(hpccg_hip_matrix* M, int nrhs, const double* B, long l
 int hpccg_hip_batch_last_trace(const hpccg_hip_matrix* M, int col, double* out, int cap)
 {
     if (!M || !out) return fail(HPCCG_HIP_EINVAL, "batch: NULL argument");
-    const Workspace* w = find_workspace(M);
+    const Workspace* w = g_ws<Workspace>.find(M);
     if (!w || col < 0 || col >= (int)w->trace.size())
         return fail(HPCCG_HIP_EINVAL, "batch: no trace of column %d (the last batch solve had %d)", col,
                     w ? (int)w->trace.size() : 0);
@@ -1317,14 +871,14 @@ int hpccg_hip_batch_sparsemv(hpccg_hip_matrix* M, int nrhs, const double* X_dev,
 int hpccg_hip_batch_release(hpccg_hip_matrix* M)
 {
     if (!M) return fail(HPCCG_HIP_EINVAL, "batch: NULL argument");
-    drop_workspace(M);
+    g_ws<Workspace>.drop(M);
     return 0;
 }
 
 int hpccg_hip_batch_workspace_bytes(const hpccg_hip_matrix* M, long long* bytes)
 {
     if (!M || !bytes) return fail(HPCCG_HIP_EINVAL, "batch: NULL argument");
-    const Workspace* w = find_workspace(M);
+    const Workspace* w = g_ws<Workspace>.find(M);
     *bytes = w ? w->bytes : 0;
     return 0;
 }
@@ -1332,8 +886,7 @@ int hpccg_hip_batch_workspace_bytes(const hpccg_hip_matrix* M, long long* bytes)
 int hpccg_hip_batch_live_workspaces(int* count)
 {
     if (!count) return fail(HPCCG_HIP_EINVAL, "batch: NULL argument");
-    std::lock_guard<std::mutex> lk(g_mu);
-    *count = (int)g_ws.size();
+    *count = g_ws<Workspace>.live();
     return 0;
 }
 

@@ -1,8 +1,8 @@
 // hpccg_device.h -- device pieces shared by the kernel translation units
-// (hpccg_kernels.hip, hpccg_batch.hip): the row-blocked vector access and the
-// fixed-shape reductions. Every rounding shape of a dot product exists once,
-// here, so a kernel of either unit that sums the same values gets the same
-// bits. Internal linkage (each unit inlines its own copy); device code only.
+// (hpccg_kernels.hip, hpccg_batch.hip, hpccg_mixed.hip; the latter two through
+// hpccg_columns.h): the row-blocked vector access and the fixed-shape
+// reductions. Every rounding shape of a dot product exists once, here, so a
+// kernel of any unit that sums the same values gets the same bits. Internal linkage (each unit inlines its own copy); device code only.
 #pragma once
 #include "hpccg_internal.h"
 

@@ -20,32 +20,28 @@
 //
 //   convert   k_mixed_convert: fp64 image -> fp32 image, counts the values that
 //             do not survive the round trip and those outside fp32 range
-//   SpMM      k_mixed_spmm_a<kW, kR> | k_mixed_spmm_sell<kR>: the batch
-//             library's slot loops over the fp32 image, kR = 1, 2, 4 columns
-//   p update, update, finalize: the batch library's shapes (hpccg_batch.hip),
-//             with the loop test's tolerance and iteration limit per column
+//   SpMM      k_mixed_spmm_a<kW, kR> | k_mixed_spmm_sell<kR>: the fp64 slot
+//             loops over the fp32 image, kR = 1, 2, 4 columns
+//   p update, update, finalize: k_mixed_p, k_mixed_update, k_mixed_finalize
+//             over the column engine's bodies (hpccg_columns.h), the loop
+//             test's tolerance and iteration limit set per column by the host
 //   residual  k_mixed_residual: r = b - A x from an fp64 A x with the r.r slice
 //             partials | x = x + d (refinement)
-// Every dot keeps the rounding shape of hpccg_device.h. Launches are eager on
-// the matrix's stream; every kCheckEvery iterations the host reads one word
-// (columns ended). No kernel here waits on another block.
+// The recurrence itself -- the column's state, those bodies, the workspace
+// registry and the launch loop -- is hpccg_columns.h; this unit adds the fp32
+// image, its SpMM loops and the refinement. Every dot keeps the rounding shape
+// of hpccg_device.h. No kernel here waits on another block.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cfloat>
 #include <chrono>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <map>
-#include <mutex>
 #include <vector>
 
 #include "../../include/hpccg_hip_mixed.h"
-#include "hpccg_device.h"
-#include "hpccg_internal.h"
+#include "hpccg_columns.h"
 
 #pragma clang fp contract(off)
 
@@ -53,60 +49,14 @@ namespace hpccg {
 
 namespace {
 
-// Per-column scalar state of the running recurrence: set by the host before a
-// recurrence starts, advanced by k_mixed_finalize only.
-struct ColState {
-    double rtrans;     // r_{k-1}.r_{k-1} of the iteration k about to run (HPCCG.cpp: rtrans)
-    double oldrtrans;  // r_{k-2}.r_{k-2}
-    double pap;        // p_k.Ap_k
-    double alpha;      // rtrans / pap
-    double beta;       // rtrans / oldrtrans (0.0 for k = 1)
-    double tol;        // the loop test's tolerance of this column's recurrence
-    int k;             // the iteration about to run (0: the prologue)
-    int run;           // 1: iteration k runs; 0: the column is frozen
-    int niters;        // iterations done once the recurrence has ended
-    int max_iter;      // the loop test's iteration limit of this column's recurrence
-};
-
-enum Dot : int { kDotRR = 0, kDotPAP = 1 };
-
-struct MixedArgs {
-    int n, nslices, grid;
-    int nrhs;      // columns of the call
-    int c0;        // first column of this launch (it covers c0 .. c0 + kR - 1, those < nrhs)
-    int cap;       // columns the workspace holds (stride of the partials)
-    int ng;        // ceil(nslices / kGroup)
-    int force;     // 1: every column runs whatever its state (the plain SpMM)
-    int nt, a_width;
-    double* p;     // local row 0 of column 0; column c at p + c * pcs (a zeroed guard zone around each)
-    long long xsell;  // SELL-512 column 0 relative to local row 0
-    double* r;     // column c at r + c * vcs, as Ap, x, b, ox, ob
-    double* Ap;
-    double* x;     // the recurrence's unknown (exact: the caller's x; refinement: the correction d)
-    double* b;     // the recurrence's right-hand side (exact: the caller's b; refinement: r_s)
-    double* ox;    // the caller's x
-    double* ob;    // the caller's b
-    long long pcs, vcs;
-    double* partial;  // [2][cap][nslices] slice partials (r.r, then p.Ap)
-    double* gsum;     // [2][cap][ng] group sums (beyond the finalize block's LDS only)
-    double* tot;      // [cap] r.r totals of the residual step
-    ColState* st;     // [cap]
-    double* hist;     // [cap][hstride]: hist[c][k] = r_k.r_k
-    long long hstride;
-    int* ended;       // columns whose loop has ended
+struct MixedArgs : ColArgs {
+    // (ColArgs' x and b: the caller's, ox and ob, where the fp32 image is the
+    // matrix; the refinement's correction d and residual r_s otherwise; tot:
+    // [cap] r.r totals of the residual step)
+    double* ox;        // the caller's x
+    double* ob;        // the caller's b
     const float* img;  // the fp32 values (layout above)
-    const int* aoff;
-    const unsigned int* abase;
-    const unsigned int* slice_base;
-    const int* cols;
 };
-
-// Wave-uniform table loads through the scalar cache (tables no kernel writes).
-template <class T>
-__device__ __forceinline__ T sld(const T* p)
-{
-    return *(const __attribute__((address_space(4))) T*)(p);
-}
 
 typedef float f4v __attribute__((ext_vector_type(4)));
 typedef float f2v __attribute__((ext_vector_type(2)));
@@ -127,26 +77,6 @@ __device__ __forceinline__ f2v ld_f2(const float* __restrict__ p)
         return __builtin_nontemporal_load(reinterpret_cast<const f2v*>(p));
     else
         return *reinterpret_cast<const f2v*>(p);
-}
-
-template <int kR>
-__device__ __forceinline__ bool active_cols(const MixedArgs& a, bool (&act)[kR], bool& all)
-{
-    bool any = false;
-    all = true;
-#pragma unroll
-    for (int j = 0; j < kR; j++) {
-        const int c = a.c0 + j;
-        act[j] = c < a.nrhs && (a.force || a.st[c].run != 0);
-        any = any || act[j];
-        all = all && act[j];
-    }
-    return any;
-}
-
-__device__ __forceinline__ double* slice_partials(const MixedArgs& a, int which, int c)
-{
-    return a.partial + ((size_t)which * a.cap + c) * (size_t)a.nslices;
 }
 
 // ---------------------------------------------------------------------------
@@ -186,61 +116,10 @@ __global__ __launch_bounds__(kBlock) void k_mixed_convert(const double* __restri
     if (range) atomicAdd(flags + 1, (unsigned long long)range);
 }
 
-// ---------------------------------------------------------------------------
-// p = x + 0.0*x (prologue, HPCCG.cpp:347) | p = r + beta*p (k == 1 reads r for
-// p, beta 0.0), per running column (k_batch_p's expressions).
-// ---------------------------------------------------------------------------
 template <int kR>
 __global__ __launch_bounds__(kBlock) void k_mixed_p(MixedArgs a, bool prologue)
 {
-    const int s = xcd_slice(a.grid);
-    if (s >= a.nslices) return;
-    const int row = s * kSliceRows + threadIdx.x * kRpt;
-#pragma unroll
-    for (int j = 0; j < kR; j++) {
-        const int c = a.c0 + j;
-        if (c >= a.nrhs) break;
-        if (!a.st[c].run) continue;  // (block-uniform)
-        double* __restrict__ pc = a.p + (size_t)c * a.pcs;
-        Rows o;
-        if (prologue) {
-            const Rows xv = ld(a.x + (size_t)c * a.vcs + row);
-#pragma unroll
-            for (int i = 0; i < kRpt; i++) o.v[i] = xv.v[i] + 0.0 * xv.v[i];
-        } else {
-            const int k = a.st[c].k;
-            const double beta = a.st[c].beta;
-            const Rows rv = ld(a.r + (size_t)c * a.vcs + row);
-            const Rows yv = (k == 1) ? rv : ld(pc + row);
-#pragma unroll
-            for (int i = 0; i < kRpt; i++) o.v[i] = rv.v[i] + beta * yv.v[i];
-        }
-        st_rows(pc, row, a.n, o);
-    }
-}
-
-// The SpMM epilogue of one column's two rows: store Ap; the rows' p.Ap terms
-// in spmv_rows_out's order, the slice partial by block_sum (the batch
-// library's spmm_rows_out).
-template <int kR>
-__device__ __forceinline__ void spmm_rows_out(const MixedArgs& a, bool prologue, int s, int row, const bool (&act)[kR],
-                                              const double (&sum)[kR][kRpt])
-{
-#pragma unroll
-    for (int j = 0; j < kR; j++) {
-        if (!act[j]) continue;  // (block-uniform)
-        const int c = a.c0 + j;
-        st_rows(a.Ap + (size_t)c * a.vcs, row, a.n, Rows{{sum[j][0], sum[j][1]}});
-        if (prologue) continue;  // HPCCG.cpp:351: the prologue SpMV has no p.Ap
-        const Rows pv = ld(a.p + (size_t)c * a.pcs + row);
-        double d = 0.0;
-#pragma unroll
-        for (int i = 0; i < kRpt; i++)
-            if (row + i < a.n) d += pv.v[i] * sum[j][i];
-        const double bs = block_sum<kBlock>(d);
-        if (threadIdx.x == 0) slice_partials(a, kDotPAP, c)[s] = bs;
-        __syncthreads();  // block_sum's LDS words are free for the next column
-    }
+    col_p<kR>(a, prologue);
 }
 
 // One slot of the A image for every column: sum[c][i] = sum[c][i] +
@@ -380,51 +259,10 @@ __global__ __launch_bounds__(kBlock) void k_mixed_spmm_sell(MixedArgs a, bool pr
     spmm_rows_out<kR>(a, prologue, s, row, act, sum);
 }
 
-// ---------------------------------------------------------------------------
-// prologue: r = b + (-1)*Ap                         (HPCCG.cpp:352)
-// loop:     x = x + alpha*p; r = r + (-alpha)*Ap    (HPCCG.cpp:382-384)
-// then the r.r slice partial, per running column (k_batch_update's expressions).
-// ---------------------------------------------------------------------------
 template <int kR>
 __global__ __launch_bounds__(kBlock) void k_mixed_update(MixedArgs a, bool prologue)
 {
-    const int s = xcd_slice(a.grid);
-    if (s >= a.nslices) return;
-    const int row = s * kSliceRows + threadIdx.x * kRpt;
-#pragma unroll
-    for (int j = 0; j < kR; j++) {
-        const int c = a.c0 + j;
-        if (c >= a.nrhs) break;
-        if (!a.st[c].run) continue;  // (block-uniform)
-        double* __restrict__ rc = a.r + (size_t)c * a.vcs;
-        const Rows apv = ld(a.Ap + (size_t)c * a.vcs + row);
-        Rows rn;
-        if (prologue) {
-            const Rows bv = ld(a.b + (size_t)c * a.vcs + row);
-#pragma unroll
-            for (int i = 0; i < kRpt; i++) rn.v[i] = bv.v[i] + (-1.0) * apv.v[i];
-        } else {
-            const double alpha = a.st[c].alpha;
-            const Rows rv = ld(rc + row);
-#pragma unroll
-            for (int i = 0; i < kRpt; i++) rn.v[i] = rv.v[i] + (-alpha) * apv.v[i];
-            double* __restrict__ xc = a.x + (size_t)c * a.vcs;
-            const Rows xv = ld(xc + row);
-            const Rows pv = ld(a.p + (size_t)c * a.pcs + row);
-            Rows xn;
-#pragma unroll
-            for (int i = 0; i < kRpt; i++) xn.v[i] = xv.v[i] + alpha * pv.v[i];
-            st_rows(xc, row, a.n, xn);
-        }
-        st_rows(rc, row, a.n, rn);
-        double d = 0.0;
-#pragma unroll
-        for (int i = 0; i < kRpt; i++)
-            if (row + i < a.n) d += rn.v[i] * rn.v[i];
-        const double bs = block_sum<kBlock>(d);
-        if (threadIdx.x == 0) slice_partials(a, kDotRR, c)[s] = bs;
-        __syncthreads();  // block_sum's LDS words are free for the next column
-    }
+    col_update<kR>(a, prologue);
 }
 
 // ---------------------------------------------------------------------------
@@ -457,126 +295,20 @@ __global__ __launch_bounds__(kBlock) void k_mixed_residual(MixedArgs a, int corr
 #pragma unroll
         for (int i = 0; i < kRpt; i++) rn.v[i] = bv.v[i] + (-1.0) * av.v[i];
         st_rows(a.b + co, row, a.n, rn);
-        double d = 0.0;
-#pragma unroll
-        for (int i = 0; i < kRpt; i++)
-            if (row + i < a.n) d += rn.v[i] * rn.v[i];
-        const double bs = block_sum<kBlock>(d);
-        if (threadIdx.x == 0) slice_partials(a, kDotRR, c)[s] = bs;
-        __syncthreads();  // block_sum's LDS words are free for the next column
+        rr_slice_partial(a, s, row, c, rn);
     }
 }
 
-// ---------------------------------------------------------------------------
-// One block per column: the dot's two upper levels (k_batch_finalize's shapes),
-// then the column's scalars with the column's own tolerance and limit.
-//   p.Ap: alpha = rtrans / p.Ap                       (HPCCG.cpp:381-382)
-//   r.r of iteration k: hist[k]; oldrtrans, rtrans, beta for iteration k + 1
-//         and its loop test k + 1 < max_iter && normr > tol, normr being the
-//         value iteration k computed, sqrt(r_{k-1}.r_{k-1}) (HPCCG.cpp:358;
-//         sqrt(r_0.r_0) for k + 1 = 1).
-// total_only (the refinement's residual step): the total is stored in tot[c]
-// and the state is left alone.
-// ---------------------------------------------------------------------------
-constexpr int kFinThreads = 1024;
-constexpr int kFinLds = 2048;  // group sums kept in LDS up to 128 K slices
-
-__device__ __forceinline__ void advance_column(const MixedArgs& a, ColState* st, int c, int which, double tot)
+// store_total (the refinement's residual step): the r.r total is stored in
+// tot[c] and the state is left alone.
+__global__ __launch_bounds__(kFinThreads) void k_mixed_finalize(MixedArgs a, int which, int store_total)
 {
-    if (which == kDotPAP) {
-        st->pap = tot;
-        st->alpha = st->rtrans / tot;
-        return;
-    }
-    const int k = st->k;
-    const double old = st->rtrans;  // r_{k-1}.r_{k-1} (k >= 1)
-    a.hist[(size_t)c * a.hstride + k] = tot;
-    st->oldrtrans = old;
-    st->rtrans = tot;
-    st->beta = (k == 0) ? 0.0 : tot / old;
-    st->k = k + 1;
-    const bool run = k + 1 < st->max_iter && sqrt(k == 0 ? tot : old) > st->tol;
-    if (!run) {
-        st->run = 0;
-        st->niters = k;
-        atomicAdd(a.ended, 1);
-    }
-}
-
-__global__ __launch_bounds__(kFinThreads) void k_mixed_finalize(MixedArgs a, int which, int total_only)
-{
-    __shared__ double gs[kFinLds];
-    const int c = blockIdx.x;
-    ColState* const st = a.st + c;
-    if (!st->run) return;  // (block-uniform) a frozen column keeps its state
-    const int ng = a.ng;
-    const bool in_lds = ng <= kFinLds;
-    const double* const sp = slice_partials(a, which, c);
-    double* const gp = a.gsum + ((size_t)which * a.cap + c) * (size_t)ng;
-    const int lane = threadIdx.x & (kWave - 1);
-    constexpr int kWaves = kFinThreads / kWave;
-    constexpr int kB = 4;  // groups per wave per round, their loads issued before the sums
-    for (int g0 = threadIdx.x / kWave; g0 < ng; g0 += kWaves * kB) {
-        double v[kB];
-#pragma unroll
-        for (int b = 0; b < kB; b++) {
-            const int g = g0 + b * kWaves;
-            const int i = g * kGroup + lane;
-            v[b] = (g < ng && i < a.nslices) ? sp[i] : 0.0;
-        }
-#pragma unroll
-        for (int b = 0; b < kB; b++) {
-            const int g = g0 + b * kWaves;
-            const double w = wave_sum(v[b]);
-            if (lane == 0 && g < ng) {
-                if (in_lds)
-                    gs[g] = w;
-                else
-                    gp[g] = w;
-            }
-        }
-    }
-    if (!in_lds) __threadfence_block();
-    __syncthreads();  // group sums written by this block
-    if (threadIdx.x >= kWave) return;
-    const double tot = in_lds ? top_sum_wave([&](int i) { return gs[i]; }, ng, lane)
-                              : top_sum_wave([gp](int i) { return gp[i]; }, ng, lane);
-    if (lane != 0) return;
-    if (total_only) {
-        a.tot[c] = tot;
-        return;
-    }
-    advance_column(a, st, c, which, tot);
+    col_finalize(a, which, store_total);
 }
 
 // ---------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------
-int fail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return hpccg_hip_internal_set_error(code, buf);
-}
-
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return fail(e_ == hipErrorOutOfMemory ? HPCCG_HIP_ENOMEM : HPCCG_HIP_EHIP,         \
-                        "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);   \
-    } while (0)
-
-#define TRY(expr)                     \
-    do {                              \
-        int rc_ = (expr);             \
-        if (rc_ != 0) return rc_;     \
-    } while (0)
-
-constexpr int kCheckEvery = 32;  // iterations between two reads of the "columns ended" word
 constexpr double kInnerRtolDefault = 0x1p-20;
 
 // What the last solve did on one column.
@@ -586,98 +318,30 @@ struct ColRecord {
     std::vector<double> resid;  // rho_s, then the final residual
 };
 
-struct Workspace {
-    MatrixView v;
+struct Workspace : ColWorkspace {
     // the fp32 image
     float* img = nullptr;
     long long img_bytes = 0;
     bool built = false;
     long long inexact = 0, out_of_range = 0;
-    // the vectors
-    int cap = 0;  // columns
-    bool refine = false;  // ob, ox are buffers of their own
-    long long pcs = 0, vcs = 0;
-    double *pbuf = nullptr, *r = nullptr, *Ap = nullptr, *x = nullptr, *b = nullptr, *ox = nullptr, *ob = nullptr;
-    double *partial = nullptr, *gsum = nullptr, *tot = nullptr;
-    ColState* st = nullptr;
-    int* ended = nullptr;
-    double* hist = nullptr;
-    long long hstride = 0;
-    int* h_ended = nullptr;  // pinned
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    long long bytes = 0;  // of the vectors
+    // the vectors of its own
+    bool refine = false;  // x, b are buffers of their own (the refinement's d, r_s)
+    double *r = nullptr, *x = nullptr, *b = nullptr, *ox = nullptr, *ob = nullptr;
     std::vector<ColState> hst;
     std::vector<ColRecord> rec;  // per column of the last solve
-};
 
-std::mutex g_mu;
-std::map<const hpccg_hip_matrix*, Workspace*> g_ws;
-
-void free_vectors(Workspace* w)
-{
-    if (w->v.stream) (void)hipStreamSynchronize(w->v.stream);
-    for (void* q : {(void*)w->pbuf, (void*)w->r, (void*)w->Ap, (void*)w->x, (void*)w->b, (void*)w->ox, (void*)w->ob,
-                    (void*)w->partial, (void*)w->gsum, (void*)w->tot, (void*)w->st, (void*)w->ended, (void*)w->hist})
-        if (q) (void)hipFree(q);
-    w->pbuf = w->r = w->Ap = w->x = w->b = w->ox = w->ob = w->partial = w->gsum = w->tot = w->hist = nullptr;
-    w->st = nullptr;
-    w->ended = nullptr;
-    w->cap = 0;
-    w->refine = false;
-    w->hstride = 0;
-    w->bytes = 0;
-}
-
-void drop_workspace(const hpccg_hip_matrix* M)
-{
-    Workspace* w = nullptr;
+    void free_own_vectors()
     {
-        std::lock_guard<std::mutex> lk(g_mu);
-        auto it = g_ws.find(M);
-        if (it == g_ws.end()) return;
-        w = it->second;
-        g_ws.erase(it);
+        for (double* q : {r, x, b, ox, ob})
+            if (q) (void)hipFree(q);
+        r = x = b = ox = ob = nullptr;
+        refine = false;
     }
-    (void)hipSetDevice(w->v.device);
-    free_vectors(w);
-    if (w->img) (void)hipFree(w->img);
-    if (w->h_ended) (void)hipHostFree(w->h_ended);
-    if (w->ev0) (void)hipEventDestroy(w->ev0);
-    if (w->ev1) (void)hipEventDestroy(w->ev1);
-    delete w;
-}
-
-// the destroy hook (ctx: the matrix, the workspace's key; a no-op once released)
-void on_matrix_destroy(void* ctx) { drop_workspace(static_cast<const hpccg_hip_matrix*>(ctx)); }
-
-Workspace* find_workspace(const hpccg_hip_matrix* M)
-{
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto it = g_ws.find(M);
-    return it == g_ws.end() ? nullptr : it->second;
-}
-
-// The matrix's workspace record (made on first use, with the destroy hook).
-int get_record(hpccg_hip_matrix* M, const MatrixView& v, Workspace** out)
-{
-    Workspace* w = find_workspace(M);
-    if (!w) {
-        w = new Workspace;
-        {
-            std::lock_guard<std::mutex> lk(g_mu);
-            g_ws[M] = w;
-        }
-        w->v = v;
-        const int rc = hpccg_hip_internal_on_destroy(M, on_matrix_destroy, M);
-        if (rc) {
-            drop_workspace(M);
-            return rc;
-        }
+    void free_own_rest()
+    {
+        if (img) (void)hipFree(img);
     }
-    w->v = v;
-    *out = w;
-    return 0;
-}
+};
 
 int out_of_range(const Workspace* w)
 {
@@ -735,58 +399,22 @@ int ensure_image(Workspace* w)
     return 0;
 }
 
-template <class T>
-int alloc_zero(Workspace* w, T** p, size_t count)
-{
-    const size_t bytes = sizeof(T) * std::max<size_t>(count, 1);
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), bytes));
-    HIP_TRY(hipMemsetAsync(*p, 0, bytes, w->v.stream));
-    w->bytes += (long long)bytes;
-    return 0;
-}
-
 // Room for ncols columns and a history of max_iter + 1 entries per column;
 // refine: the refinement's two further vectors per column.
 int ensure_vectors(Workspace* w, int ncols, int max_iter, bool refine)
 {
-    const MatrixView& v = w->v;
-    HIP_TRY(hipSetDevice(v.device));
-    if (!w->h_ended) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&w->h_ended), sizeof(int), hipHostMallocDefault));
-    if (!w->ev0) HIP_TRY(hipEventCreate(&w->ev0));
-    if (!w->ev1) HIP_TRY(hipEventCreate(&w->ev1));
-    const long long hneed = (long long)max_iter + 1;
-    if (ncols <= w->cap && hneed <= w->hstride && (w->refine || !refine)) return 0;
-    const int cap = std::max(ncols, w->cap);
-    const long long hstride = std::max(hneed, w->hstride);
     refine = refine || w->refine;
-    free_vectors(w);
-    const size_t npad = (size_t)v.npad;
-    const size_t ng = (size_t)(v.nslices + kGroup - 1) / kGroup;
-    w->pcs = (long long)(npad + 2 * (size_t)v.guard_rows);  // a p column: [guard | rows (padded) | guard]
-    w->vcs = (long long)npad;
-    // zeroed: p's guard zones and the rows past n are read (holes, full-width
-    // loads) and never stored by a kernel
-    int rc = alloc_zero(w, &w->pbuf, (size_t)w->pcs * cap);
-    if (!rc) rc = alloc_zero(w, &w->r, npad * cap);
-    if (!rc) rc = alloc_zero(w, &w->Ap, npad * cap);
-    if (!rc) rc = alloc_zero(w, &w->ox, npad * cap);
-    if (!rc) rc = alloc_zero(w, &w->ob, npad * cap);
-    if (!rc && refine) rc = alloc_zero(w, &w->x, npad * cap);
-    if (!rc && refine) rc = alloc_zero(w, &w->b, npad * cap);
-    if (!rc) rc = alloc_zero(w, &w->partial, 2 * (size_t)cap * std::max(v.nslices, 1));
-    if (!rc) rc = alloc_zero(w, &w->gsum, 2 * (size_t)cap * std::max<size_t>(ng, 1));
-    if (!rc) rc = alloc_zero(w, &w->tot, (size_t)cap);
-    if (!rc) rc = alloc_zero(w, &w->st, (size_t)cap);
-    if (!rc) rc = alloc_zero(w, &w->ended, 1);
-    if (!rc) rc = alloc_zero(w, &w->hist, (size_t)cap * (size_t)hstride);
-    if (rc) {
-        free_vectors(w);
-        return rc;
-    }
-    w->cap = cap;
-    w->refine = refine;
-    w->hstride = hstride;
-    return 0;
+    const size_t npad = (size_t)w->v.npad;
+    const long long pcs = (long long)(npad + 2 * (size_t)w->v.guard_rows);  // a p column: [guard | rows (padded) | guard]
+    return ensure_columns(w, ncols, max_iter, refine == w->refine, pcs, 1, [&](int cap) {
+        TRY(alloc_zero(w, &w->r, npad * cap));
+        TRY(alloc_zero(w, &w->ox, npad * cap));
+        TRY(alloc_zero(w, &w->ob, npad * cap));
+        if (refine) TRY(alloc_zero(w, &w->x, npad * cap));
+        if (refine) TRY(alloc_zero(w, &w->b, npad * cap));
+        w->refine = refine;
+        return 0;
+    });
 }
 
 // What the mixed library runs on: one rank, no halo.
@@ -803,55 +431,18 @@ int check_matrix(hpccg_hip_matrix* M, MatrixView* v)
 // inner: the recurrence runs on the refinement's (r_s, d) instead of (b, x)
 MixedArgs make_args(const Workspace* w, int nrhs, bool inner)
 {
-    const MatrixView& v = w->v;
-    MixedArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.n = v.n;
-    a.nslices = v.nslices;
-    a.grid = v.grid;
-    a.nrhs = nrhs;
-    a.cap = w->cap;
-    a.ng = (v.nslices + kGroup - 1) / kGroup;
-    a.nt = v.nt && !std::getenv("HPCCG_MIXED_NO_NT");  // (diagnostics: the A/B of the non-temporal value loads)
-    a.a_width = v.a_width;
-    a.p = w->pbuf + v.guard_rows;
-    a.xsell = v.sell_col_base;
+    MixedArgs a{};
+    fill_args(&a, w, nrhs);
+    a.nt = a.nt && !std::getenv("HPCCG_MIXED_NO_NT");  // (diagnostics: the A/B of the non-temporal value loads)
+    a.p = w->pbuf + w->v.guard_rows;
     a.r = w->r;
-    a.Ap = w->Ap;
+    a.rcs = w->vcs;
     a.ox = w->ox;
     a.ob = w->ob;
     a.x = inner ? w->x : w->ox;
     a.b = inner ? w->b : w->ob;
-    a.pcs = w->pcs;
-    a.vcs = w->vcs;
-    a.partial = w->partial;
-    a.gsum = w->gsum;
-    a.tot = w->tot;
-    a.st = w->st;
-    a.hist = w->hist;
-    a.hstride = w->hstride;
-    a.ended = w->ended;
     a.img = w->img;
-    a.aoff = v.aoff;
-    a.abase = v.abase;
-    a.slice_base = v.slice_base;
-    a.cols = v.cols;
     return a;
-}
-
-// Columns [c0, c0 + kR) per launch: fours, a remainder of three as a four with
-// one idle column (one pass over the matrix, not two), of two as a two, of one
-// as a one (the single column is the main use: its own instantiation).
-template <class F>
-void for_chunks(int nrhs, F f)
-{
-    int c0 = 0;
-    while (nrhs - c0 >= 3) {
-        f(c0, 4);
-        c0 += 4;
-    }
-    if (nrhs - c0 == 2) f(c0, 2);
-    if (nrhs - c0 == 1) f(c0, 1);
 }
 
 #define HPCCG_MIXED_R(KERNEL, ...)                                                         \
@@ -868,7 +459,7 @@ void launch_spmm(const Workspace* w, MixedArgs a, bool prologue)
 {
     const dim3 g(a.grid), b(kBlock);
     hipStream_t s = w->v.stream;
-    for_chunks(a.nrhs, [&](int c0, int R) {
+    for_chunks(a.nrhs, true, [&](int c0, int R) {
         a.c0 = c0;
 #define HPCCG_MIXED_NT(KERNEL, ...)                      \
     do {                                                \
@@ -893,7 +484,7 @@ void launch_p(const Workspace* w, MixedArgs a, bool prologue)
 {
     const dim3 g(a.grid), b(kBlock);
     hipStream_t s = w->v.stream;
-    for_chunks(a.nrhs, [&](int c0, int R) {
+    for_chunks(a.nrhs, true, [&](int c0, int R) {
         a.c0 = c0;
         HPCCG_MIXED_R(k_mixed_p, );
     });
@@ -903,27 +494,16 @@ void launch_update(const Workspace* w, MixedArgs a, bool prologue)
 {
     const dim3 g(a.grid), b(kBlock);
     hipStream_t s = w->v.stream;
-    for_chunks(a.nrhs, [&](int c0, int R) {
+    for_chunks(a.nrhs, true, [&](int c0, int R) {
         a.c0 = c0;
         HPCCG_MIXED_R(k_mixed_update, );
     });
 }
 #undef HPCCG_MIXED_R
 
-void launch_finalize(const Workspace* w, const MixedArgs& a, int which, int total_only = 0)
+void launch_finalize(const Workspace* w, const MixedArgs& a, int which, int store_total = 0)
 {
-    hipLaunchKernelGGL(k_mixed_finalize, dim3(a.nrhs), dim3(kFinThreads), 0, w->v.stream, a, which, total_only);
-}
-
-// Columns between the caller's column-major array and the workspace (kind:
-// host or device on the caller's side), stream-ordered.
-int copy_cols(const Workspace* w, double* dst, long long ldd, const double* src, long long lds, int nrhs,
-              hipMemcpyKind kind)
-{
-    for (int c = 0; c < nrhs; c++)
-        HIP_TRY(hipMemcpyAsync(dst + (size_t)c * (size_t)ldd, src + (size_t)c * (size_t)lds,
-                               sizeof(double) * (size_t)w->v.n, kind, w->v.stream));
-    return 0;
+    hipLaunchKernelGGL(k_mixed_finalize, dim3(a.nrhs), dim3(kFinThreads), 0, w->v.stream, a, which, store_total);
 }
 
 // The columns' states for the next launches: column c runs (fresh, with its
@@ -948,7 +528,6 @@ int set_states(Workspace* w, int nrhs, const std::vector<char>& run, const std::
 int run_cg(Workspace* w, const MixedArgs& a, const std::vector<char>& run, const std::vector<int>& max_iter,
            std::vector<int>& it)
 {
-    hipStream_t s = w->v.stream;
     const int nrhs = a.nrhs;
     int nrun = 0, kmax = 1;
     for (int c = 0; c < nrhs; c++)
@@ -956,41 +535,12 @@ int run_cg(Workspace* w, const MixedArgs& a, const std::vector<char>& run, const
             nrun++;
             kmax = std::max(kmax, max_iter[c]);
         }
-    launch_p(w, a, true);
-    launch_spmm(w, a, true);
-    launch_update(w, a, true);
-    launch_finalize(w, a, kDotRR);
-    HIP_TRY(hipGetLastError());
-    for (int k = 1; k < kmax; k++) {
-        launch_p(w, a, false);
-        launch_spmm(w, a, false);
-        launch_finalize(w, a, kDotPAP);
-        launch_update(w, a, false);
-        launch_finalize(w, a, kDotRR);
-        if (k % kCheckEvery == 0 && k + 1 < kmax) {
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(w->h_ended, w->ended, sizeof(int), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            if (*w->h_ended >= nrun) break;  // later launches would be no-ops for every column
-        }
-    }
-    HIP_TRY(hipGetLastError());
-    std::vector<ColState> st(nrhs);
-    std::vector<double> hist((size_t)nrhs * (size_t)w->hstride);
-    HIP_TRY(hipMemcpyAsync(st.data(), w->st, sizeof(ColState) * nrhs, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(hist.data(), w->hist, sizeof(double) * hist.size(), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (int c = 0; c < nrhs; c++) {
-        if (!run[c]) continue;
-        // a column still running when the launches ran out did max_iter - 1 iterations
-        const int n = st[c].run ? st[c].k - 1 : st[c].niters;
-        const double* h = hist.data() + (size_t)c * (size_t)w->hstride;
-        // normr after iteration k is sqrt(r_{k-1}.r_{k-1}) (HPCCG.cpp:371): the single solve's trace
-        std::vector<double>& tr = w->rec[c].trace;
-        tr.push_back(std::sqrt(h[0]));
-        for (int k = 1; k <= n; k++) tr.push_back(std::sqrt(h[k - 1]));
-        it[c] = n;
-    }
+    TRY(run_recurrence(w, a, nrun, kmax, launch_p, launch_spmm, launch_update, launch_finalize));
+    std::vector<ColState> st;
+    std::vector<double> hist;
+    TRY(read_columns(w, nrhs, &st, &hist));
+    for (int c = 0; c < nrhs; c++)
+        if (run[c]) it[c] = column_trace(st[c], hist.data() + (size_t)c * (size_t)w->hstride, &w->rec[c].trace);
     return 0;
 }
 
@@ -1064,17 +614,6 @@ int run_solve(hpccg_hip_matrix* M, Workspace* w, int nrhs, int max_iter, double 
     }
 }
 
-// f() with the caller's current device put back afterwards
-template <class F>
-int keep_device(F f)
-{
-    int cur = 0;
-    HIP_TRY(hipGetDevice(&cur));
-    const int rc = f();
-    (void)hipSetDevice(cur);
-    return rc;
-}
-
 int solve_common(hpccg_hip_matrix* M, int nrhs, const double* B, long long ldb, double* X, long long ldx, int max_iter,
                  double tol, int max_sweeps, double inner_rtol, int* niters, double* normr, double* times, bool host)
 {
@@ -1100,7 +639,7 @@ int solve_common(hpccg_hip_matrix* M, int nrhs, const double* B, long long ldb, 
     if (max_iter < 1) max_iter = 1;
     return keep_device([&]() -> int {
         Workspace* w = nullptr;
-        TRY(get_record(M, v, &w));
+        TRY(g_ws<Workspace>.record(M, v, &w));
         TRY(ensure_image(w));
         TRY(ensure_vectors(w, nrhs, max_iter, w->inexact != 0));
         const hipMemcpyKind in = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
@@ -1129,7 +668,7 @@ int solve_common(hpccg_hip_matrix* M, int nrhs, const double* B, long long ldb, 
 
 const ColRecord* find_record(const hpccg_hip_matrix* M, int col, const char* what)
 {
-    const Workspace* w = find_workspace(M);
+    const Workspace* w = g_ws<Workspace>.find(M);
     if (!w || col < 0 || col >= (int)w->rec.size()) {
         fail(HPCCG_HIP_EINVAL, "mixed: no %s of column %d (the last mixed solve had %d)", what, col,
              w ? (int)w->rec.size() : 0);
@@ -1176,7 +715,7 @@ int hpccg_hip_mixed_sparsemv(hpccg_hip_matrix* M, int nrhs, const double* X_dev,
     if (v.n == 0) return 0;
     return keep_device([&]() -> int {
         Workspace* w = nullptr;
-        TRY(get_record(M, v, &w));
+        TRY(g_ws<Workspace>.record(M, v, &w));
         TRY(ensure_image(w));
         TRY(ensure_vectors(w, nrhs, 1, false));
         // x into the guarded p columns, Ap = A~ p, Ap out
@@ -1201,7 +740,7 @@ int hpccg_hip_mixed_info(hpccg_hip_matrix* M, long long out[4])
     if (v.n == 0) return 0;
     return keep_device([&]() -> int {
         Workspace* w = nullptr;
-        TRY(get_record(M, v, &w));
+        TRY(g_ws<Workspace>.record(M, v, &w));
         TRY(ensure_image(w));
         out[0] = w->inexact == 0 ? 1 : 0;
         out[1] = w->img_bytes;
@@ -1235,14 +774,14 @@ int hpccg_hip_mixed_last_sweeps(const hpccg_hip_matrix* M, int col, int* iters, 
 int hpccg_hip_mixed_release(hpccg_hip_matrix* M)
 {
     if (!M) return fail(HPCCG_HIP_EINVAL, "mixed: NULL argument");
-    drop_workspace(M);
+    g_ws<Workspace>.drop(M);
     return 0;
 }
 
 int hpccg_hip_mixed_workspace_bytes(const hpccg_hip_matrix* M, long long* bytes)
 {
     if (!M || !bytes) return fail(HPCCG_HIP_EINVAL, "mixed: NULL argument");
-    const Workspace* w = find_workspace(M);
+    const Workspace* w = g_ws<Workspace>.find(M);
     *bytes = w ? w->bytes + w->img_bytes : 0;
     return 0;
 }
@@ -1250,8 +789,7 @@ int hpccg_hip_mixed_workspace_bytes(const hpccg_hip_matrix* M, long long* bytes)
 int hpccg_hip_mixed_live_workspaces(int* count)
 {
     if (!count) return fail(HPCCG_HIP_EINVAL, "mixed: NULL argument");
-    std::lock_guard<std::mutex> lk(g_mu);
-    *count = (int)g_ws.size();
+    *count = g_ws<Workspace>.live();
     return 0;
 }
 

@@ -232,6 +232,54 @@ def mixed_lib() -> C.CDLL:
     return L
 
 
+PCG_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_pcg.so")
+_pcg_lib = None
+
+
+def pcg_lib() -> C.CDLL:
+    """Load libhpccg_hip_pcg.so (include/hpccg_hip_pcg.h) on first use. It is
+    linked against libhpccg_hip.so beside it, so lib() is loaded first and both
+    share one copy of the main library."""
+    global _pcg_lib
+    if _pcg_lib is not None:
+        return _pcg_lib
+    if os.environ.get("HPCCG_HIP_LIB", LIB_PATH) != LIB_PATH:
+        raise HPCCGError("the pcg library runs on the in-tree libhpccg_hip.so only (HPCCG_HIP_LIB is set)")
+    lib()
+    if not os.path.exists(PCG_LIB_PATH):
+        raise HPCCGError(f"{PCG_LIB_PATH} missing: run build() (the preconditioned solve has no fallback)")
+    try:
+        L = C.CDLL(PCG_LIB_PATH)
+    except OSError as e:
+        raise HPCCGError(f"{PCG_LIB_PATH} does not load: {e}") from e
+    vp, ip, dp, lp = C.c_void_p, C.c_int, C.c_double, C.c_longlong
+    PI, PD = C.POINTER(C.c_int), C.POINTER(C.c_double)
+    sig = {
+        "hpccg_hip_pcg_abi_version": (ip, []),
+        "hpccg_hip_pcg_solve_device": (ip, [vp, ip, vp, lp, vp, lp, vp, ip, dp, PI, PD, PD]),
+        "hpccg_hip_pcg_solve": (ip, [vp, ip, vp, lp, vp, lp, vp, ip, dp, PI, PD, PD]),
+        "hpccg_hip_pcg_diagonal": (ip, [vp, vp]),
+        "hpccg_hip_pcg_last_trace": (ip, [vp, ip, PD, ip]),
+        "hpccg_hip_pcg_release": (ip, [vp]),
+        "hpccg_hip_pcg_workspace_bytes": (ip, [vp, C.POINTER(lp)]),
+        "hpccg_hip_pcg_live_workspaces": (ip, [PI]),
+    }
+    for name, (res, args) in sig.items():
+        f = getattr(L, name)
+        f.restype = res
+        f.argtypes = args
+    _pcg_lib = L
+    return L
+
+
+def pcg_exported_symbols() -> list[str]:
+    """Functions include/hpccg_hip_pcg.h declares (checked by the CPU suite)."""
+    import re
+    with open(os.path.join(ROOT, "include", "hpccg_hip_pcg.h")) as f:
+        text = f.read()
+    return sorted(set(re.findall(r"\b(hpccg_hip_pcg_\w+)\s*\(", text)))
+
+
 def mixed_exported_symbols() -> list[str]:
     """Functions include/hpccg_hip_mixed.h declares (checked by the CPU suite)."""
     import re
@@ -562,6 +610,35 @@ class Matrix:
         _check(_mixed_lib.hpccg_hip_mixed_workspace_bytes(self.h, C.byref(v)), "mixed_workspace_bytes")
         return v.value
 
+    def diagonal_pcg(self) -> np.ndarray:
+        """The matrix's diagonal as the preconditioned solve reads it from the
+        device image (0.0 where a row stores none)."""
+        import torch
+        n = int(self.info()["nrow"])
+        d = torch.zeros(max(n, 1), dtype=torch.float64, device="cuda")
+        _check(pcg_lib().hpccg_hip_pcg_diagonal(self.h, _ptr(d)), "diagonal_pcg")
+        return d.cpu().numpy()[:n].copy()
+
+    def last_trace_pcg(self, col: int, cap: int = 100000) -> np.ndarray:
+        """Residual trace (norm of r) of column col of the last HPCCG_pcg on this matrix."""
+        out = np.zeros(cap, np.float64)
+        n = pcg_lib().hpccg_hip_pcg_last_trace(self.h, int(col), out.ctypes.data_as(C.POINTER(C.c_double)), cap)
+        if n < 0:
+            _check(n, "last_trace_pcg")
+        return out[:n]
+
+    def pcg_release(self) -> None:
+        """Free this matrix's pcg workspace (with its cached 1 / a_ii) now (close() does it too)."""
+        if self.h and _pcg_lib is not None:
+            _check(_pcg_lib.hpccg_hip_pcg_release(self.h), "pcg_release")
+
+    def pcg_workspace_bytes(self) -> int:
+        if _pcg_lib is None:
+            return 0
+        v = C.c_longlong(0)
+        _check(_pcg_lib.hpccg_hip_pcg_workspace_bytes(self.h, C.byref(v)), "pcg_workspace_bytes")
+        return v.value
+
     def close(self):
         # (a batch workspace goes with the matrix: the library's destroy hook,
         # whether or not the batch library was ever loaded)
@@ -739,6 +816,58 @@ def mixed_live_workspaces() -> int:
         return 0
     c = C.c_int(0)
     _check(_mixed_lib.hpccg_hip_mixed_live_workspaces(C.byref(c)), "mixed_live_workspaces")
+    return c.value
+
+
+# ---------------------------------------------------------------------------
+# diagonally preconditioned solve (include/hpccg_hip_pcg.h)
+# ---------------------------------------------------------------------------
+def HPCCG_pcg(M: Matrix, B, X, max_iter: int = 500, tolerance: float = 0.0, minv=None, device=False, nrhs=None,
+              ldb=None, ldx=None):
+    """nrhs preconditioned CG solves against M with M^-1 = diag(minv)
+    (hpccg_hip_pcg_solve[_device]); minv None is Jacobi, 1 / a_ii. The loop
+    test, niters and normr are on the 2-norm of r, as in HPCCG. B, X: as
+    HPCCG_batch (a 1-D array or tensor is one column); minv: nrow entries, all
+    finite and > 0 -- numpy on the host or, with device=True, a tensor / device
+    pointer. X is updated in place. Returns (ierr, niters[nrhs], normr[nrhs],
+    times)."""
+    L = pcg_lib()
+    B, X = _one_column(B, "B"), _one_column(X, "X")
+    bp, nb, ldb_ = _cols(B, nrhs, ldb, "B")
+    xp, nx_, ldx_ = _cols(X, nrhs, ldx, "X")
+    if nb != nx_:
+        raise HPCCGError(f"B holds {nb} columns, X {nx_}")
+    if not device and not (isinstance(B, np.ndarray) and isinstance(X, np.ndarray)):
+        raise HPCCGError("host solve: B and X are numpy arrays")
+    mp, keep = None, None
+    if minv is not None:
+        nrow = int(M.info()["nrow"])
+        if device:
+            if not isinstance(minv, int) and (minv.dim() != 1 or minv.shape[0] < nrow or
+                                              (minv.shape[0] > 1 and minv.stride(0) != 1)):
+                raise HPCCGError(f"minv: a contiguous 1-D tensor of {nrow} entries")
+            mp = _ptr(minv)
+        else:
+            keep = np.ascontiguousarray(minv, np.float64)
+            if keep.ndim != 1 or keep.shape[0] < nrow:
+                raise HPCCGError(f"minv: a 1-D array of {nrow} entries")
+            mp = keep.ctypes.data
+    it = np.zeros(max(nb, 1), np.int32)
+    nr = np.zeros(max(nb, 1), np.float64)
+    times = np.zeros(7, np.float64)
+    f = L.hpccg_hip_pcg_solve_device if device else L.hpccg_hip_pcg_solve
+    rc = f(M.h, nb, bp, ldb_, xp, ldx_, mp, max_iter, tolerance, it.ctypes.data_as(C.POINTER(C.c_int)),
+           nr.ctypes.data_as(C.POINTER(C.c_double)), times.ctypes.data_as(C.POINTER(C.c_double)))
+    _check(rc, "HPCCG_pcg")
+    return rc, it[:nb], nr[:nb], times
+
+
+def pcg_live_workspaces() -> int:
+    """Matrices that hold a pcg workspace (0 when the library was never loaded)."""
+    if _pcg_lib is None:
+        return 0
+    c = C.c_int(0)
+    _check(_pcg_lib.hpccg_hip_pcg_live_workspaces(C.byref(c)), "pcg_live_workspaces")
     return c.value
 
 

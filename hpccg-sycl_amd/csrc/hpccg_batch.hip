@@ -23,8 +23,8 @@
 // waits on another block.
 // The recurrence itself -- the column's state, the bodies of the p update, the
 // SpMM epilogue, the update and the finalize, the workspace registry and the
-// launch loop -- is hpccg_columns.h; this unit adds the fp64 SpMM loops, the
-// guarded p / r layout and the group.
+// launch loop -- is hpccg_columns.h, the fp64 SpMM loops are hpccg_spmm.h; this
+// unit adds the guarded p / r layout and the group.
 //
 // Over an in-process rank group (include/hpccg_hip_batch_group.h; the last part
 // of the host code): every member runs these kernels on its rows, the ghost
@@ -43,6 +43,7 @@
 #include "../../include/hpccg_hip_batch.h"
 #include "../../include/hpccg_hip_batch_group.h"
 #include "hpccg_columns.h"
+#include "hpccg_spmm.h"
 
 #pragma clang fp contract(off)
 
@@ -66,7 +67,7 @@ __global__ void k_batch_init(BatchArgs a, int max_iter, double tol)
     if (c == 0) *a.ended = 0;
     if (c >= a.nrhs) return;
     ColState s;
-    s.rtrans = s.oldrtrans = s.pap = s.alpha = s.beta = 0.0;
+    s.rtrans = s.oldrtrans = s.rr = s.pap = s.alpha = s.beta = 0.0;
     s.tol = tol;
     s.k = 0;
     s.run = 1;
@@ -81,79 +82,8 @@ __global__ __launch_bounds__(kBlock) void k_batch_p(BatchArgs a, bool prologue)
     col_p<kR>(a, prologue);
 }
 
-// ---------------------------------------------------------------------------
-// SpMM over SELL-512-A: k_spmv_a's slot loop with kR running sums per row. A
-// value slot pair is loaded once; column c's x is p_c at the slice's offsets
-// (holes: 0.0 times a finite word of p_c's zeroed guard zone or a real
-// neighbour). Per row and column the products are added in slot order with no
-// contraction: the single kernel's row sum.
-// ---------------------------------------------------------------------------
-template <int kW, int kR, bool kNT, bool kAll>
-__device__ __forceinline__ void spmm_a_slots(const BatchArgs& a, const double* __restrict__ vp,
-                                             const int* __restrict__ off, int wdt, const double* __restrict__ xr,
-                                             const bool (&act)[kR], double (&sum)[kR][kRpt])
-{
-#pragma unroll kW > 0 ? kW : 4
-    for (int j = 0; j < wdt; j++) {
-        const Rows v = ld_m<kNT>(vp + (size_t)j * kSliceRows);
-        const int oj = sld(off + j);
-#pragma unroll
-        for (int c = 0; c < kR; c++) {
-            if (kAll || act[c]) {
-                const Rows xv = ld_u(xr + ((long long)c * a.pcs + oj));
-#pragma unroll
-                for (int i = 0; i < kRpt; i++) sum[c][i] = sum[c][i] + v.v[i] * xv.v[i];
-            }
-        }
-    }
-}
-
-// The x-triple plan of the 27-point width (k_spmv_a's kTri, here for nine
-// triples): an interior slice's ascending offsets come in runs o - 1, o, o + 1
-// (the x neighbours of each of the nine (y, z) neighbours). One 16-B load of
-// the centre pair serves the run: row 2t's left neighbour and row 2t + 1's
-// right neighbour come from the adjacent lanes (wave_shr1 / wave_shl1), lanes 0
-// and 63 load their one outside value. The same x values in the same products
-// in slot order: the same bits, a third of the x loads. With kR columns the
-// gathers, not the value stream, set this kernel's time (27 x kR 16-B loads per
-// thread from L2; 200^3, four columns: 616 us a launch against 430 us for its
-// bytes at the update kernel's rate). Same-box A/B of the plan, two rounds:
-// 200^3 four columns 3803 -> 4008 RHS-iterations/s, 100^3 29 970 -> 30 620
-// (DESIGN.md 10).
-constexpr int kTriples = 9;
-
-template <int kR, bool kNT>
-__device__ __forceinline__ void spmm_a_triples(const BatchArgs& a, const double* __restrict__ vp,
-                                               const int* __restrict__ off, const double* __restrict__ xr,
-                                               double (&sum)[kR][kRpt])
-{
-    const int lane = threadIdx.x & (kWave - 1);
-    // (one run of kR columns in flight per thread: fully unrolled the
-    // scheduler hoists every load of the slice, 280-430 VGPRs; three runs 158)
-#pragma unroll 1
-    for (int g = 0; g < kTriples; g++) {
-        const Rows v0 = ld_m<kNT>(vp + (size_t)(3 * g) * kSliceRows);
-        const Rows v1 = ld_m<kNT>(vp + (size_t)(3 * g + 1) * kSliceRows);
-        const Rows v2 = ld_m<kNT>(vp + (size_t)(3 * g + 2) * kSliceRows);
-        const int o = sld(off + 3 * g + 1);  // the run's centre offset
-#pragma unroll
-        for (int c = 0; c < kR; c++) {
-            const double* __restrict__ xc = xr + ((long long)c * a.pcs + o);
-            const Rows ctr = ld_u(xc);
-            double left = wave_shr1(ctr.v[1]);
-            double right = wave_shl1(ctr.v[0]);
-            if (lane == 0) left = xc[-1];
-            if (lane == kWave - 1) right = xc[2];
-            sum[c][0] = sum[c][0] + v0.v[0] * left;
-            sum[c][1] = sum[c][1] + v0.v[1] * ctr.v[0];
-            sum[c][0] = sum[c][0] + v1.v[0] * ctr.v[0];
-            sum[c][1] = sum[c][1] + v1.v[1] * ctr.v[1];
-            sum[c][0] = sum[c][0] + v2.v[0] * ctr.v[1];
-            sum[c][1] = sum[c][1] + v2.v[1] * right;
-        }
-    }
-}
-
+// The SpMM loops are hpccg_spmm.h's (shared with hpccg_pcg.hip); the entry
+// points set the launch shape.
 // kWaves: the occupancy the kernel is compiled for (waves per SIMD). The
 // 27-wide four-column form exists twice: at 5 (92 VGPRs) for images streamed
 // from HBM and at 4 (102) for images the Infinity Cache holds -- same box,
@@ -163,91 +93,13 @@ template <int kW, int kR, int kWaves = 4>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWaves))) void k_batch_spmm_a(BatchArgs a,
                                                                                                      bool prologue)
 {
-    const int s = xcd_slice(a.grid);
-    if (s >= a.nslices) return;
-    bool act[kR], all;
-    if (!active_cols<kR>(a, act, all)) return;
-    const int wdt = kW > 0 ? kW : (int)(sld(a.abase + s + 1) - sld(a.abase + s));
-    const size_t vb = kW > 0 ? (size_t)s * kW : (size_t)sld(a.abase + s);
-    const double* __restrict__ vp = a.aval + vb * kSliceRows + (size_t)threadIdx.x * kRpt;
-    const int* __restrict__ off = a.aoff + (size_t)s * kAMax;
-    const int row = s * kSliceRows + threadIdx.x * kRpt;
-    const double* __restrict__ xr = a.p + (size_t)a.c0 * a.pcs + row;  // column c0 + c: x of column row + off at xr[c * pcs + off]
-    double sum[kR][kRpt];
-#pragma unroll
-    for (int c = 0; c < kR; c++)
-#pragma unroll
-        for (int i = 0; i < kRpt; i++) sum[c][i] = 0.0;
-    bool tri = false;
-    // (four columns only: with two the plan's registers cost the kernel a wave
-    // per SIMD, 200^3 1.20x the sequential solves against 1.23x without it)
-    constexpr bool kTri = kW == 3 * kTriples && kR >= 4;
-    if constexpr (kTri) {
-        tri = all && a.tri;
-#pragma unroll
-        for (int g = 0; g < kTriples; g++) {
-            const int o0 = sld(off + 3 * g);
-            tri = tri && sld(off + 3 * g + 1) == o0 + 1 && sld(off + 3 * g + 2) == o0 + 2;
-        }
-    }
-    if (tri) {  // (block-uniform)
-        if constexpr (kTri) {
-            if (a.nt)
-                spmm_a_triples<kR, true>(a, vp, off, xr, sum);
-            else
-                spmm_a_triples<kR, false>(a, vp, off, xr, sum);
-        }
-    } else if (all) {
-        if (a.nt)
-            spmm_a_slots<kW, kR, true, true>(a, vp, off, wdt, xr, act, sum);
-        else
-            spmm_a_slots<kW, kR, false, true>(a, vp, off, wdt, xr, act, sum);
-    } else {
-        spmm_a_slots<kW, kR, false, false>(a, vp, off, wdt, xr, act, sum);
-    }
-    spmm_rows_out<kR>(a, prologue, s, row, act, sum);
+    spmm_a_body<kW, kR>(a, prologue);
 }
 
-// ---------------------------------------------------------------------------
-// SpMM over SELL-512 (int32 columns; matrices without an A image): k_spmv_sell's
-// loop, x gathered from p_c. Padding slots (column -1, value 0) add +0.
-// ---------------------------------------------------------------------------
 template <int kR>
 __global__ __launch_bounds__(kBlock) void k_batch_spmm_sell(BatchArgs a, bool prologue)
 {
-    const int s = xcd_slice(a.grid);
-    if (s >= a.nslices) return;
-    bool act[kR], all;
-    if (!active_cols<kR>(a, act, all)) return;
-    const size_t base = (size_t)sld(a.slice_base + s) * kSliceRows + (size_t)threadIdx.x * kRpt;
-    const int w = (int)(sld(a.slice_base + s + 1) - sld(a.slice_base + s));
-    const double* __restrict__ vp = a.vals + base;
-    const int* __restrict__ cp = a.cols + base;
-    const double* __restrict__ x0 = a.p + ((long long)a.c0 * a.pcs + a.xsell);
-    double sum[kR][kRpt];
-#pragma unroll
-    for (int c = 0; c < kR; c++)
-#pragma unroll
-        for (int i = 0; i < kRpt; i++) sum[c][i] = 0.0;
-#pragma unroll 3
-    for (int j = 0; j < w; j++) {
-        typedef int i2v __attribute__((ext_vector_type(2)));
-        const i2v ct = *reinterpret_cast<const i2v*>(cp + (size_t)j * kSliceRows);
-        const int col[kRpt] = {ct.x, ct.y};
-        const Rows v = ld(vp + (size_t)j * kSliceRows);
-#pragma unroll
-        for (int c = 0; c < kR; c++) {
-            if (!act[c]) continue;  // (block-uniform)
-            const double* __restrict__ x = x0 + (size_t)c * a.pcs;
-#pragma unroll
-            for (int i = 0; i < kRpt; i++) {
-                const double xv = (col[i] >= 0) ? x[col[i]] : 0.0;
-                sum[c][i] = sum[c][i] + v.v[i] * xv;
-            }
-        }
-    }
-    const int row = s * kSliceRows + threadIdx.x * kRpt;
-    spmm_rows_out<kR>(a, prologue, s, row, act, sum);
+    spmm_sell_body<kR>(a, prologue);
 }
 
 template <int kR>
@@ -288,7 +140,7 @@ __global__ void k_batch_group_sum(BatchArgs a, GroupTotals g, int which)
     if (!s.run) return;  // frozen on every member
     double v = 0.0;
     for (int r = 0; r < g.nranks; r++) v += g.tot[r][(size_t)which * g.cap[r] + c];
-    advance_column(a, &s, c, which, v);
+    advance_column(a, &s, c, which, v, v);
     for (int r = 0; r < g.nranks; r++) g.st[r][c] = s;
 }
 

@@ -1,13 +1,17 @@
 // hpccg_columns.h -- the column-recurrence engine shared by the multi-column
-// units (hpccg_batch.hip, hpccg_mixed.hip): one CG recurrence per column of a
-// call, each with the single solve's expressions and the single solve's dot
-// shape (hpccg_device.h). Every rounding-relevant expression at column level
-// and the loop test exist once, here, so column c of either library is bitwise
-// the single solve of it.
+// units (hpccg_batch.hip, hpccg_mixed.hip, hpccg_pcg.hip): one CG recurrence
+// per column of a call, each with the single solve's expressions and the
+// single solve's dot shape (hpccg_device.h). Every rounding-relevant expression
+// at column level and the loop test exist once, here, so column c of the batch
+// or the mixed library is bitwise the single solve of it. The bodies' kPre
+// forms are the diagonally preconditioned recurrence (hpccg_pcg.hip): the same
+// statements with z = m r in r's place where the recurrence asks for z, and a
+// second dot, r.z, beside r.r; with m = 1 they are the plain ones bit for bit.
 //   device  ColState, ColArgs; the bodies of the p update, the SpMM epilogue,
 //           the update with its r.r slice partial and the finalize. A unit's
 //           __global__ entry points are thin wrappers over them; its SpMM loops
-//           (value type, load shape: the tuned part) are its own.
+//           (value type, load shape: the tuned part) are its own or
+//           hpccg_spmm.h's.
 //   host    error helpers, the workspace registry, the shared vector set with
 //           its grow-or-keep logic, the eager launch loop of one recurrence and
 //           the history -> trace read-back.
@@ -36,9 +40,14 @@ namespace {
 // Per-column scalar state of the running recurrence: set before it starts (a
 // kernel or an upload of the unit's), advanced by the finalize only (a group
 // member's: by the group's sum only).
+//   Preconditioned (kPre; m the unit's positive vector, z = m r never stored):
+// rtrans and oldrtrans hold r.z, which alpha and beta are made of, and rr holds
+// r.r, which the history and the loop test are made of. Unpreconditioned the
+// two are one number, stored twice.
 struct ColState {
-    double rtrans;     // r_{k-1}.r_{k-1} of the iteration k about to run (HPCCG.cpp: rtrans)
-    double oldrtrans;  // r_{k-2}.r_{k-2}
+    double rtrans;     // r_{k-1}.z_{k-1} of the iteration k about to run (HPCCG.cpp: rtrans)
+    double oldrtrans;  // r_{k-2}.z_{k-2}
+    double rr;         // r_{k-1}.r_{k-1}
     double pap;        // p_k.Ap_k
     double alpha;      // rtrans / pap
     double beta;       // rtrans / oldrtrans (0.0 for k = 1)
@@ -49,7 +58,8 @@ struct ColState {
     int max_iter;      // the loop test's iteration limit of this column's recurrence
 };
 
-enum Dot : int { kDotRR = 0, kDotPAP = 1 };
+// (kDotRZ: the preconditioned recurrence's r.z partials, completed by the r.r finalize)
+enum Dot : int { kDotRR = 0, kDotPAP = 1, kDotRZ = 2 };
 
 // What every kernel of a unit takes (the unit's own struct adds its matrix values).
 struct ColArgs {
@@ -67,8 +77,9 @@ struct ColArgs {
     double* x;     // the recurrence's unknown
     double* b;     // the recurrence's right-hand side
     long long pcs, vcs, rcs;
-    double* partial;  // [2][cap][nslices] slice partials (r.r, then p.Ap)
-    double* gsum;     // [2][cap][ng] group sums (beyond the finalize block's LDS only)
+    const double* minv;  // preconditioned: m, one entry per row, shared by the columns (else unused)
+    double* partial;  // [ndots][cap][nslices] slice partials (r.r, then p.Ap; preconditioned: then r.z)
+    double* gsum;     // [ndots][cap][ng] group sums (beyond the finalize block's LDS only)
     double* tot;      // [which][cap] dot totals the finalize stores instead of advancing the state
     ColState* st;     // [cap]
     double* hist;     // [cap][hstride]: hist[c][k] = r_k.r_k
@@ -110,13 +121,18 @@ __device__ __forceinline__ double* slice_partials(const ColArgs& a, int which, i
 // ---------------------------------------------------------------------------
 // p = x + 0.0*x (prologue, HPCCG.cpp:347) | p = r + beta*p (k_p_update's
 // expression: k == 1 reads r for p, beta 0.0), per running column.
+// kPre: p = z + beta*p with z = m*r formed in the register (k == 1: z for p);
+// m is loaded once for the launch's columns.
 // ---------------------------------------------------------------------------
-template <int kR>
+template <int kR, bool kPre = false>
 __device__ __forceinline__ void col_p(const ColArgs& a, bool prologue)
 {
     const int s = xcd_slice(a.grid);
     if (s >= a.nslices) return;
     const int row = s * kSliceRows + threadIdx.x * kRpt;
+    Rows mv{};
+    if constexpr (kPre)
+        if (!prologue) mv = ld(a.minv + row);
 #pragma unroll
     for (int j = 0; j < kR; j++) {
         const int c = a.c0 + j;
@@ -131,7 +147,11 @@ __device__ __forceinline__ void col_p(const ColArgs& a, bool prologue)
         } else {
             const int k = a.st[c].k;
             const double beta = a.st[c].beta;
-            const Rows rv = ld(a.r + (size_t)c * a.rcs + row);
+            Rows rv = ld(a.r + (size_t)c * a.rcs + row);
+            if constexpr (kPre) {
+#pragma unroll
+                for (int i = 0; i < kRpt; i++) rv.v[i] = mv.v[i] * rv.v[i];  // z
+            }
             const Rows yv = (k == 1) ? rv : ld(pc + row);
 #pragma unroll
             for (int i = 0; i < kRpt; i++) o.v[i] = rv.v[i] + beta * yv.v[i];
@@ -163,29 +183,41 @@ __device__ __forceinline__ void spmm_rows_out(const ColArgs& a, bool prologue, i
     }
 }
 
-// The r.r slice partial of column c from this thread's two rows of r.
-__device__ __forceinline__ void rr_slice_partial(const ColArgs& a, int s, int row, int c, const Rows& rn)
+// The slice partial `which` of column c from this thread's two rows of r and
+// of w: sum of r_i * w_i (r.r: w = r; r.z: w = z).
+__device__ __forceinline__ void rw_slice_partial(const ColArgs& a, int which, int s, int row, int c, const Rows& rn,
+                                                 const Rows& wn)
 {
     double d = 0.0;
 #pragma unroll
     for (int i = 0; i < kRpt; i++)
-        if (row + i < a.n) d += rn.v[i] * rn.v[i];
+        if (row + i < a.n) d += rn.v[i] * wn.v[i];
     const double bs = block_sum<kBlock>(d);
-    if (threadIdx.x == 0) slice_partials(a, kDotRR, c)[s] = bs;
+    if (threadIdx.x == 0) slice_partials(a, which, c)[s] = bs;
     __syncthreads();  // block_sum's LDS words are free for the next column
+}
+
+// The r.r slice partial of column c from this thread's two rows of r.
+__device__ __forceinline__ void rr_slice_partial(const ColArgs& a, int s, int row, int c, const Rows& rn)
+{
+    rw_slice_partial(a, kDotRR, s, row, c, rn, rn);
 }
 
 // ---------------------------------------------------------------------------
 // prologue: r = b + (-1)*Ap                         (HPCCG.cpp:352)
 // loop:     x = x + alpha*p; r = r + (-alpha)*Ap    (HPCCG.cpp:382-384)
 // then the r.r slice partial (k_update's expressions), per running column.
+// kPre: also the r.z slice partial, sum of r_i * (m_i * r_i), in the same pass;
+// m is loaded once for the launch's columns.
 // ---------------------------------------------------------------------------
-template <int kR>
+template <int kR, bool kPre = false>
 __device__ __forceinline__ void col_update(const ColArgs& a, bool prologue)
 {
     const int s = xcd_slice(a.grid);
     if (s >= a.nslices) return;
     const int row = s * kSliceRows + threadIdx.x * kRpt;
+    Rows mv{};
+    if constexpr (kPre) mv = ld(a.minv + row);
 #pragma unroll
     for (int j = 0; j < kR; j++) {
         const int c = a.c0 + j;
@@ -212,6 +244,12 @@ __device__ __forceinline__ void col_update(const ColArgs& a, bool prologue)
             st_rows(xc, row, a.n, xn);
         }
         st_rows(rc, row, a.n, rn);
+        if constexpr (kPre) {
+            Rows zn;
+#pragma unroll
+            for (int i = 0; i < kRpt; i++) zn.v[i] = mv.v[i] * rn.v[i];
+            rw_slice_partial(a, kDotRZ, s, row, c, rn, zn);
+        }
         rr_slice_partial(a, s, row, c, rn);
     }
 }
@@ -222,7 +260,10 @@ __device__ __forceinline__ void col_update(const ColArgs& a, bool prologue)
 //         and its loop test k + 1 < max_iter && normr > tol, normr being the
 //         value iteration k computed, sqrt(r_{k-1}.r_{k-1}) (HPCCG.cpp:358,
 //         as cg_run restates it; sqrt(r_0.r_0) for k + 1 = 1).
-__device__ __forceinline__ void advance_column(const ColArgs& a, ColState* st, int c, int which, double tot)
+//   rr: the r.r total beside the r.z total tot of a preconditioned recurrence
+//         (hist and the loop test are r.r's, alpha and beta r.z's); else tot
+//         itself. Unused for p.Ap.
+__device__ __forceinline__ void advance_column(const ColArgs& a, ColState* st, int c, int which, double tot, double rr)
 {
     if (which == kDotPAP) {
         st->pap = tot;
@@ -230,13 +271,15 @@ __device__ __forceinline__ void advance_column(const ColArgs& a, ColState* st, i
         return;
     }
     const int k = st->k;
-    const double old = st->rtrans;  // r_{k-1}.r_{k-1} (k >= 1)
-    a.hist[(size_t)c * a.hstride + k] = tot;
+    const double old = st->rtrans;  // r_{k-1}.z_{k-1} (k >= 1)
+    const double oldrr = st->rr;    // r_{k-1}.r_{k-1} (k >= 1)
+    a.hist[(size_t)c * a.hstride + k] = rr;
     st->oldrtrans = old;
     st->rtrans = tot;
+    st->rr = rr;
     st->beta = (k == 0) ? 0.0 : tot / old;
     st->k = k + 1;
-    const bool run = k + 1 < st->max_iter && sqrt(k == 0 ? tot : old) > st->tol;
+    const bool run = k + 1 < st->max_iter && sqrt(k == 0 ? rr : oldrr) > st->tol;
     if (!run) {
         st->run = 0;
         st->niters = k;
@@ -255,12 +298,10 @@ __device__ __forceinline__ void advance_column(const ColArgs& a, ColState* st, i
 constexpr int kFinThreads = 1024;
 constexpr int kFinLds = 2048;  // group sums kept in LDS up to 128 K slices
 
-__device__ __forceinline__ void col_finalize(const ColArgs& a, int which, int store_total)
+// The total of column c's dot `which` from its slice partials, by the whole
+// block (gs: its kFinLds LDS words); valid in thread 0.
+__device__ __forceinline__ double col_dot_total(const ColArgs& a, int which, int c, double* gs)
 {
-    __shared__ double gs[kFinLds];
-    const int c = blockIdx.x;
-    ColState* const st = a.st + c;
-    if (!st->run) return;  // (block-uniform) a frozen column keeps its state
     const int ng = a.ng;
     const bool in_lds = ng <= kFinLds;
     const double* const sp = slice_partials(a, which, c);
@@ -290,15 +331,34 @@ __device__ __forceinline__ void col_finalize(const ColArgs& a, int which, int st
     }
     if (!in_lds) __threadfence_block();
     __syncthreads();  // group sums written by this block
-    if (threadIdx.x >= kWave) return;
-    const double tot = in_lds ? top_sum_wave([&](int i) { return gs[i]; }, ng, lane)
-                              : top_sum_wave([gp](int i) { return gp[i]; }, ng, lane);
-    if (lane != 0) return;
+    if (threadIdx.x >= kWave) return 0.0;
+    return in_lds ? top_sum_wave([&](int i) { return gs[i]; }, ng, lane)
+                  : top_sum_wave([gp](int i) { return gp[i]; }, ng, lane);
+}
+
+// kPre: the r.r finalize completes the r.z total too (the update kernel's two
+// slice partials), and the column advances once on both.
+template <bool kPre = false>
+__device__ __forceinline__ void col_finalize(const ColArgs& a, int which, int store_total)
+{
+    __shared__ double gs[kFinLds];
+    const int c = blockIdx.x;
+    ColState* const st = a.st + c;
+    if (!st->run) return;  // (block-uniform) a frozen column keeps its state
+    const double tot = col_dot_total(a, which, c, gs);
+    double rz = tot;
+    if constexpr (kPre) {
+        if (which == kDotRR) {  // (block-uniform)
+            __syncthreads();    // the r.r group sums in gs have been read
+            rz = col_dot_total(a, kDotRZ, c, gs);
+        }
+    }
+    if (threadIdx.x != 0) return;
     if (store_total) {
         a.tot[(size_t)which * a.cap + c] = tot;
         return;
     }
-    advance_column(a, st, c, which, tot);
+    advance_column(a, st, c, which, rz, tot);
 }
 
 // ---------------------------------------------------------------------------
@@ -348,6 +408,7 @@ int keep_device(F f)
 struct ColWorkspace {
     MatrixView v;
     int cap = 0;  // columns
+    int ndots = 2;  // dots with slice partials per column (a preconditioned unit: 3, r.z)
     long long pcs = 0, vcs = 0;
     double *pbuf = nullptr, *Ap = nullptr;
     double *partial = nullptr, *gsum = nullptr, *tot = nullptr;
@@ -487,8 +548,8 @@ int ensure_columns(W* w, int ncols, int max_iter, bool keep, long long pcs, int 
     // loads) and never stored by a kernel
     int rc = alloc_zero(w, &w->pbuf, (size_t)pcs * cap);
     if (!rc) rc = alloc_zero(w, &w->Ap, npad * cap);
-    if (!rc) rc = alloc_zero(w, &w->partial, 2 * (size_t)cap * std::max(v.nslices, 1));
-    if (!rc) rc = alloc_zero(w, &w->gsum, 2 * (size_t)cap * std::max<size_t>(ng, 1));
+    if (!rc) rc = alloc_zero(w, &w->partial, (size_t)w->ndots * cap * std::max(v.nslices, 1));
+    if (!rc) rc = alloc_zero(w, &w->gsum, (size_t)w->ndots * cap * std::max<size_t>(ng, 1));
     if (!rc && ntot) rc = alloc_zero(w, &w->tot, (size_t)ntot * cap);
     if (!rc) rc = alloc_zero(w, &w->st, (size_t)cap);
     if (!rc) rc = alloc_zero(w, &w->ended, 1);

@@ -272,6 +272,54 @@ def pcg_lib() -> C.CDLL:
     return L
 
 
+PCG_GROUP_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_pcg_group.so")
+_pcg_group_lib = None
+
+
+def pcg_group_lib() -> C.CDLL:
+    """Load libhpccg_hip_pcg_group.so (include/hpccg_hip_pcg_group.h) on first
+    use. It is linked against libhpccg_hip.so beside it, so lib() is loaded
+    first and both share one copy of the main library."""
+    global _pcg_group_lib
+    if _pcg_group_lib is not None:
+        return _pcg_group_lib
+    if os.environ.get("HPCCG_HIP_LIB", LIB_PATH) != LIB_PATH:
+        raise HPCCGError("the group pcg library runs on the in-tree libhpccg_hip.so only (HPCCG_HIP_LIB is set)")
+    lib()
+    if not os.path.exists(PCG_GROUP_LIB_PATH):
+        raise HPCCGError(f"{PCG_GROUP_LIB_PATH} missing: run build() (the group preconditioned solve has no "
+                         "fallback)")
+    try:
+        L = C.CDLL(PCG_GROUP_LIB_PATH)
+    except OSError as e:
+        raise HPCCGError(f"{PCG_GROUP_LIB_PATH} does not load: {e}") from e
+    vp, ip, dp, lp = C.c_void_p, C.c_int, C.c_double, C.c_longlong
+    PI, PD, PV, PL = C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(vp), C.POINTER(lp)
+    sig = {
+        "hpccg_hip_group_pcg_abi_version": (ip, []),
+        "hpccg_hip_group_pcg_solve_device": (ip, [PV, ip, ip, PV, PL, PV, PL, PV, ip, dp, PI, PD, PD]),
+        "hpccg_hip_group_pcg_diagonal": (ip, [PV, ip, PV]),
+        "hpccg_hip_group_pcg_last_trace": (ip, [PV, ip, ip, PD, ip]),
+        "hpccg_hip_group_pcg_release": (ip, [vp]),
+        "hpccg_hip_group_pcg_workspace_bytes": (ip, [vp, PL]),
+        "hpccg_hip_group_pcg_live_workspaces": (ip, [PI]),
+    }
+    for name, (res, args) in sig.items():
+        f = getattr(L, name)
+        f.restype = res
+        f.argtypes = args
+    _pcg_group_lib = L
+    return L
+
+
+def group_pcg_exported_symbols() -> list[str]:
+    """Functions include/hpccg_hip_pcg_group.h declares (checked by the CPU suite)."""
+    import re
+    with open(os.path.join(ROOT, "include", "hpccg_hip_pcg_group.h")) as f:
+        text = f.read()
+    return sorted(set(re.findall(r"\b(hpccg_hip_group_pcg_\w+)\s*\(", text)))
+
+
 def pcg_exported_symbols() -> list[str]:
     """Functions include/hpccg_hip_pcg.h declares (checked by the CPU suite)."""
     import re
@@ -993,6 +1041,112 @@ def group_last_trace_batch(Ms: list, col: int, cap: int = 100000) -> np.ndarray:
     if n < 0:
         _check(n, "group_last_trace_batch")
     return out[:n]
+
+
+# ---------------------------------------------------------------------------
+# preconditioned solve over an in-process group (include/hpccg_hip_pcg_group.h)
+# ---------------------------------------------------------------------------
+_HALO_COPIES_ENV = "HPCCG_GROUP_PCG_HALO_COPIES"
+
+
+def group_HPCCG_pcg(Ms: list, Bs, Xs, max_iter: int = 500, tolerance: float = 0.0, minvs=None, nrhs=None, ldb=None,
+                    ldx=None, halo_copies: bool = False):
+    """nrhs preconditioned CG solves over an in-process group with
+    M^-1 = diag(minv) (hpccg_hip_group_pcg_solve_device); minvs None is Jacobi,
+    1 / a_ii of every member's own rows, else minvs[r] is member r's nrow
+    entries (a contiguous 1-D device tensor or a device pointer), all finite
+    and > 0. The loop test, niters and normr are on the 2-norm of r, as in
+    group_HPCCG. Bs[r], Xs[r]: as group_HPCCG_batch (shape (nrhs, ld), row c
+    holding column c). Xs is updated in place. halo_copies (diagnostic): move
+    the ghost planes by one copy per column and side, as the group batch does,
+    instead of one kernel launch per member; the bits are the same. Returns
+    (niters[nrhs], normr[nrhs], times)."""
+    L = pcg_group_lib()
+    P = len(Ms)
+    if len(Bs) != P or len(Xs) != P:
+        raise HPCCGError(f"{P} members, {len(Bs)} B and {len(Xs)} X column sets")
+    hs = (C.c_void_p * P)(*[M.h for M in Ms])
+    bp, nb, ldb_ = _group_cols(Bs, nrhs, ldb, "Bs")
+    xp, nx_, ldx_ = _group_cols(Xs, nrhs, ldx, "Xs")
+    if nb != nx_:
+        raise HPCCGError(f"Bs holds {nb} columns, Xs {nx_}")
+    mp = None
+    if minvs is not None:
+        if len(minvs) != P:
+            raise HPCCGError(f"{P} members, {len(minvs)} minv vectors")
+        ptrs = []
+        for r, (M, m) in enumerate(zip(Ms, minvs)):
+            nrow = int(M.info()["nrow"])
+            if not isinstance(m, int) and (m.dim() != 1 or m.shape[0] < nrow or (m.shape[0] > 1 and m.stride(0) != 1)):
+                raise HPCCGError(f"minvs[{r}]: a contiguous 1-D tensor of {nrow} entries")
+            ptrs.append(_ptr(m))
+        mp = (C.c_void_p * P)(*ptrs)
+    it = np.zeros(max(nb, 1), np.int32)
+    nr = np.zeros(max(nb, 1), np.float64)
+    times = np.zeros(7, np.float64)
+    saved = os.environ.pop(_HALO_COPIES_ENV, None)
+    if halo_copies:
+        os.environ[_HALO_COPIES_ENV] = "1"
+    try:
+        rc = L.hpccg_hip_group_pcg_solve_device(hs, P, nb, bp, ldb_, xp, ldx_, mp, max_iter, tolerance,
+                                                it.ctypes.data_as(C.POINTER(C.c_int)),
+                                                nr.ctypes.data_as(C.POINTER(C.c_double)),
+                                                times.ctypes.data_as(C.POINTER(C.c_double)))
+    finally:
+        os.environ.pop(_HALO_COPIES_ENV, None)
+        if saved is not None:
+            os.environ[_HALO_COPIES_ENV] = saved
+    _check(rc, "group_HPCCG_pcg")
+    return it[:nb], nr[:nb], times
+
+
+def group_pcg_diagonal(Ms: list) -> list:
+    """Per member the diagonal of its rows as the group preconditioned solve
+    reads it from the member's device image (0.0 where a row stores none)."""
+    import torch
+    P = len(Ms)
+    hs = (C.c_void_p * P)(*[M.h for M in Ms])
+    ns = [int(M.info()["nrow"]) for M in Ms]
+    ds = [torch.zeros(max(n, 1), dtype=torch.float64, device="cuda") for n in ns]
+    dp = (C.c_void_p * P)(*[_ptr(d) for d in ds])
+    _check(pcg_group_lib().hpccg_hip_group_pcg_diagonal(hs, P, dp), "group_pcg_diagonal")
+    return [d.cpu().numpy()[:n].copy() for d, n in zip(ds, ns)]
+
+
+def group_last_trace_pcg(Ms: list, col: int, cap: int = 100000) -> np.ndarray:
+    """Residual trace (norm of r) of column col of the last group_HPCCG_pcg on Ms."""
+    P = len(Ms)
+    hs = (C.c_void_p * P)(*[M.h for M in Ms])
+    out = np.zeros(cap, np.float64)
+    n = pcg_group_lib().hpccg_hip_group_pcg_last_trace(hs, P, int(col), out.ctypes.data_as(C.POINTER(C.c_double)),
+                                                       cap)
+    if n < 0:
+        _check(n, "group_last_trace_pcg")
+    return out[:n]
+
+
+def group_pcg_workspace_bytes(M: Matrix) -> int:
+    """Device bytes member M's group pcg workspace holds (0: none)."""
+    if _pcg_group_lib is None:
+        return 0
+    v = C.c_longlong(0)
+    _check(_pcg_group_lib.hpccg_hip_group_pcg_workspace_bytes(M.h, C.byref(v)), "group_pcg_workspace_bytes")
+    return v.value
+
+
+def group_pcg_release(M: Matrix) -> None:
+    """Free member M's group pcg workspace (with its cached 1 / a_ii) now (close() does it too)."""
+    if M.h and _pcg_group_lib is not None:
+        _check(_pcg_group_lib.hpccg_hip_group_pcg_release(M.h), "group_pcg_release")
+
+
+def group_pcg_live_workspaces() -> int:
+    """Matrices that hold a group pcg workspace (0 when the library was never loaded)."""
+    if _pcg_group_lib is None:
+        return 0
+    c = C.c_int(0)
+    _check(_pcg_group_lib.hpccg_hip_group_pcg_live_workspaces(C.byref(c)), "group_pcg_live_workspaces")
+    return c.value
 
 
 def HPC_sparsemv(M: Matrix, x, y) -> int:

@@ -1,5 +1,5 @@
 // hpccg_columns.h -- the column-recurrence engine shared by the multi-column
-// units (hpccg_batch.hip, hpccg_mixed.hip, hpccg_pcg.hip): one CG recurrence
+// units (hpccg_batch.hip, hpccg_mixed.hip, hpccg_pcg.hip, hpccg_pcg_group.hip): one CG recurrence
 // per column of a call, each with the single solve's expressions and the
 // single solve's dot shape (hpccg_device.h). Every rounding-relevant expression
 // at column level and the loop test exist once, here, so column c of the batch
@@ -337,7 +337,8 @@ __device__ __forceinline__ double col_dot_total(const ColArgs& a, int which, int
 }
 
 // kPre: the r.r finalize completes the r.z total too (the update kernel's two
-// slice partials), and the column advances once on both.
+// slice partials), and the column advances once on both; with store_total it
+// stores both, r.z to tot[kDotRZ][c] (hpccg_pcg_group.hip: ntot = 3).
 template <bool kPre = false>
 __device__ __forceinline__ void col_finalize(const ColArgs& a, int which, int store_total)
 {
@@ -351,6 +352,8 @@ __device__ __forceinline__ void col_finalize(const ColArgs& a, int which, int st
         if (which == kDotRR) {  // (block-uniform)
             __syncthreads();    // the r.r group sums in gs have been read
             rz = col_dot_total(a, kDotRZ, c, gs);
+            // (a group member: its part of r.z beside its part of r.r below)
+            if (store_total && threadIdx.x == 0) a.tot[(size_t)kDotRZ * a.cap + c] = rz;
         }
     }
     if (threadIdx.x != 0) return;

@@ -18,7 +18,8 @@
 //   finalize  k_pcg_finalize: one block per column; the r.r launch completes
 //             both totals and advances the column once
 //   diagonal  k_pcg_diag: a_ii from the matrix image (and 1.0 / a_ii with the
-//             first row that has none) | k_pcg_check: a caller's m
+//             first row that has none) | k_pcg_check: a caller's m (the bodies
+//             and the cache of both: hpccg_jacobi.h)
 // The recurrence itself -- the column's state, those bodies (their kPre forms),
 // the workspace registry and the launch loop -- is hpccg_columns.h. No kernel
 // here waits on another block.
@@ -26,13 +27,13 @@
 
 #include <algorithm>
 #include <chrono>
-#include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <vector>
 
 #include "../../include/hpccg_hip_pcg.h"
 #include "hpccg_columns.h"
+#include "hpccg_jacobi.h"
 #include "hpccg_spmm.h"
 
 #pragma clang fp contract(off)
@@ -96,86 +97,22 @@ __global__ __launch_bounds__(kFinThreads) void k_pcg_finalize(PcgArgs a, int whi
     col_finalize<true>(a, which, store_total);
 }
 
-// ---------------------------------------------------------------------------
-// The diagonal, one block per slice, a thread its two rows: the offset-0 slot
-// of the slice (SELL-512-A; a hole there is 0.0) or the first slot whose column
-// is the row (SELL-512). d_out (may be null; any alignment): a_ii, 0.0 where
-// none is stored. minv_out (may be null; a padded vector): 1.0 / a_ii, and
-// *bad becomes the first row whose a_ii or 1.0 / a_ii is not finite and > 0.
-// ---------------------------------------------------------------------------
-struct DiagArgs {
-    int n, has_a, a_width;
-    long long xsell;
-    const double* aval;
-    const int* aoff;
-    const unsigned int* abase;
-    const unsigned int* slice_base;
-    const int* cols;
-    const double* vals;
-};
-
+// The diagonal of the image and the check of a caller's m: hpccg_jacobi.h's bodies.
 __global__ __launch_bounds__(kBlock) void k_pcg_diag(DiagArgs a, double* d_out, double* minv_out, int* bad)
 {
-    const int s = blockIdx.x;
-    const int row = s * kSliceRows + threadIdx.x * kRpt;
-    Rows d{{0.0, 0.0}};
-    if (a.has_a) {
-        const int wdt = a.a_width > 0 ? a.a_width : (int)(a.abase[s + 1] - a.abase[s]);
-        const size_t vb = a.a_width > 0 ? (size_t)s * a.a_width : (size_t)a.abase[s];
-        const int* __restrict__ off = a.aoff + (size_t)s * kAMax;
-        for (int j = 0; j < wdt; j++)
-            if (off[j] == 0) {  // (block-uniform)
-                d = ld(a.aval + (vb + j) * kSliceRows + (size_t)threadIdx.x * kRpt);
-                break;
-            }
-    } else {
-        const size_t base = (size_t)a.slice_base[s] * kSliceRows + (size_t)threadIdx.x * kRpt;
-        const int w = (int)(a.slice_base[s + 1] - a.slice_base[s]);
-        bool found[kRpt] = {false, false};
-        for (int j = 0; j < w; j++) {
-#pragma unroll
-            for (int i = 0; i < kRpt; i++) {
-                const int col = a.cols[base + (size_t)j * kSliceRows + i];
-                if (!found[i] && col >= 0 && col + a.xsell == (long long)(row + i)) {
-                    d.v[i] = a.vals[base + (size_t)j * kSliceRows + i];
-                    found[i] = true;
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < kRpt; i++) {
-        if (row + i >= a.n) continue;
-        if (d_out) d_out[row + i] = d.v[i];
-        if (minv_out) {
-            const double m = 1.0 / d.v[i];
-            minv_out[row + i] = m;
-            if (!(d.v[i] > 0.0 && isfinite(d.v[i]) && isfinite(m))) atomicMin(bad, row + i);
-        }
-    }
+    diag_body(a, d_out, minv_out, bad);
 }
 
-// *bad becomes the first row of m that is not finite and > 0.
 __global__ void k_pcg_check(const double* __restrict__ m, int n, int* bad)
 {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double v = m[i];
-    if (!(v > 0.0 && isfinite(v))) atomicMin(bad, i);
+    check_body(m, n, bad);
 }
 
 // ---------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------
-struct Workspace : ColWorkspace {
+struct Workspace : ColWorkspace, JacobiCache {
     double *r = nullptr, *x = nullptr, *b = nullptr;
-    // what stays while the columns grow: the cached 1 / a_ii (matrices are
-    // immutable), a call's own m, the "first bad row" word
-    double *jac = nullptr, *muser = nullptr;
-    int* bad = nullptr;
-    long long rest_bytes = 0;
-    bool jac_built = false;
-    int jac_bad_row = -1;
     std::vector<std::vector<double>> trace;  // per column of the last solve
 
     Workspace() { ndots = 3; }
@@ -186,11 +123,7 @@ struct Workspace : ColWorkspace {
             if (q) (void)hipFree(q);
         r = x = b = nullptr;
     }
-    void free_own_rest()
-    {
-        for (void* q : {(void*)jac, (void*)muser, (void*)bad})
-            if (q) (void)hipFree(q);
-    }
+    void free_own_rest() { free_cache(); }
 };
 
 // What the library runs on: one rank, no halo.
@@ -204,93 +137,24 @@ int check_matrix(hpccg_hip_matrix* M, MatrixView* v)
     return 0;
 }
 
-DiagArgs diag_args(const MatrixView& v)
-{
-    DiagArgs d{};
-    d.n = v.n;
-    d.has_a = v.has_a;
-    d.a_width = v.a_width;
-    d.xsell = v.sell_col_base;
-    d.aval = v.aval;
-    d.aoff = v.aoff;
-    d.abase = v.abase;
-    d.slice_base = v.slice_base;
-    d.cols = v.cols;
-    d.vals = v.vals;
-    return d;
-}
-
-// The vectors that do not depend on the number of columns (zeroed: the rows
-// past n of jac and muser are loaded and never stored).
-int ensure_rest(Workspace* w)
-{
-    if (w->jac) return 0;
-    HIP_TRY(hipSetDevice(w->v.device));
-    const size_t npad = (size_t)w->v.npad;
-    const long long before = w->bytes;  // (alloc_zero counts into bytes: the columns')
-    int rc = alloc_zero(w, &w->bad, 1);
-    if (!rc) rc = alloc_zero(w, &w->muser, npad);
-    if (!rc) rc = alloc_zero(w, &w->jac, npad);
-    w->rest_bytes += w->bytes - before;
-    w->bytes = before;
-    if (rc) {
-        w->free_own_rest();
-        w->jac = w->muser = nullptr;
-        w->bad = nullptr;
-        w->rest_bytes = 0;
-    }
-    return rc;
-}
-
-// The first bad row a check kernel found (-1: none), once the stream has run dry.
-int read_bad(Workspace* w, int* row)
-{
-    int h = INT_MAX;
-    HIP_TRY(hipMemcpyAsync(&h, w->bad, sizeof h, hipMemcpyDeviceToHost, w->v.stream));
-    HIP_TRY(hipStreamSynchronize(w->v.stream));
-    *row = h == INT_MAX ? -1 : h;
-    return 0;
-}
-
-int arm_bad(Workspace* w)
-{
-    static const int kNoRow = INT_MAX;  // above every row index
-    HIP_TRY(hipMemcpyAsync(w->bad, &kNoRow, sizeof(int), hipMemcpyHostToDevice, w->v.stream));
-    return 0;
-}
-
-// Jacobi: 1.0 / a_ii, built once per matrix on the device; the verdict on a
-// matrix it does not exist for is kept too.
+// Jacobi: the cached 1.0 / a_ii, or the refusal of a matrix it does not exist for.
 int ensure_jacobi(Workspace* w)
 {
-    if (!w->jac_built) {
-        TRY(arm_bad(w));
-        hipLaunchKernelGGL(k_pcg_diag, dim3(w->v.nslices), dim3(kBlock), 0, w->v.stream, diag_args(w->v),
-                           (double*)nullptr, w->jac, w->bad);
-        HIP_TRY(hipGetLastError());
-        TRY(read_bad(w, &w->jac_bad_row));
-        w->jac_built = true;
-    }
-    if (w->jac_bad_row >= 0)
+    int row = -1;
+    TRY(build_jacobi(w, k_pcg_diag, &row));
+    if (row >= 0)
         return fail(HPCCG_HIP_EINVAL,
                     "pcg: Jacobi needs a finite diagonal > 0 in every row; row %d is the first whose diagonal is "
                     "missing, not finite or <= 0",
-                    w->jac_bad_row);
+                    row);
     return 0;
 }
 
 // A call's own m: into the padded muser, every entry finite and > 0.
 int stage_minv(Workspace* w, const double* minv, bool host)
 {
-    hipStream_t s = w->v.stream;
-    const int n = w->v.n;
-    HIP_TRY(hipMemcpyAsync(w->muser, minv, sizeof(double) * (size_t)n, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
-                           s));
-    TRY(arm_bad(w));
-    hipLaunchKernelGGL(k_pcg_check, dim3((n + 255) / 256), dim3(256), 0, s, w->muser, n, w->bad);
-    HIP_TRY(hipGetLastError());
     int row = -1;
-    TRY(read_bad(w, &row));
+    TRY(load_minv(w, minv, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, k_pcg_check, &row));
     if (row >= 0)
         return fail(HPCCG_HIP_EINVAL, "pcg: minv[%d] is not finite and > 0 (the first such entry)", row);
     return 0;
@@ -428,7 +292,7 @@ int solve_common(hpccg_hip_matrix* M, int nrhs, const double* B, long long ldb, 
     return keep_device([&]() -> int {
         Workspace* w = nullptr;
         TRY(g_ws<Workspace>.record(M, v, &w));
-        TRY(ensure_rest(w));
+        TRY(ensure_cache(w));
         // the preconditioner first: a refused one leaves X as it is
         if (minv)
             TRY(stage_minv(w, minv, host));

@@ -587,7 +587,9 @@ int run_solve(hpccg_hip_matrix* M, Workspace* w, int nrhs, int max_iter, double 
             const double rho = std::sqrt(rr[c]);
             w->rec[c].resid.push_back(rho);
             normr[c] = rho;
-            if (rho <= tol || sweep == max_sweeps || left[c] == 0) {
+            // (a residual that is not finite or exactly zero gives the inner
+            // recurrence nothing to solve for, whatever the tolerance: x stays)
+            if (rho <= tol || !std::isfinite(rho) || rho == 0.0 || sweep == max_sweeps || left[c] == 0) {
                 live[c] = 0;
                 continue;
             }

@@ -9,9 +9,17 @@
  *
  * Parity promise: for finite B and X0, column c's x, niters, normr and residual
  * trace are bitwise those of hpccg_hip_solve_device(M, B(:,c), X(:,c), ...)
- * on that column alone. Non-finite entries in B or X0 are NOT covered: a
- * frozen or padded lane may meet them in a different order than the single
- * solve does.
+ * on that column alone.
+ *
+ * Degenerate and non-finite columns (tests/test_gpu_columns_edge.py): a column
+ * has the single solve's outcome. A zero initial residual, a NaN in b or x0, or
+ * an infinite x0 entry runs no iteration: niters 0, normr 0.0 (NaN for the
+ * non-finite ones), x untouched. A negative tolerance from a zero residual, or
+ * an infinite b entry, takes the reference's 0/0 path: niters 2, normr NaN,
+ * every x NaN. The other columns of the call are bitwise unaffected, wherever
+ * the bad one stands, and the call ends when they do. Nothing of it stays in
+ * the workspace: the next call and hpccg_hip_batch_sparsemv give their usual
+ * bits from the same vectors.
  *
  * Scope: one rank. Matrices of a communicator with more than one rank,
  * members of an in-process group and matrices with halo rows are refused with

@@ -12,8 +12,13 @@
  *
  * Parity promise: for finite B and X0, column c -- every member's x, niters,
  * normr and the residual trace -- is bitwise hpccg_hip_group_solve of that
- * column alone on the same members. Non-finite entries are not covered (see
- * hpccg_hip_batch.h).
+ * column alone on the same members. A degenerate or non-finite column (see
+ * hpccg_hip_batch.h) has hpccg_hip_group_solve's outcome on every member --
+ * niters 0 with x untouched, or niters 2 with every x NaN -- also where the bad
+ * entry lies on a plane a neighbour reads; the other columns are bitwise
+ * unaffected (a frozen column's ghost planes are copied, never used), and
+ * nothing of it stays in the members' workspaces
+ * (tests/test_gpu_columns_edge.py).
  *
  * Scope: the whole group in rank order (Ms[r] is member r, nranks the group's
  * size), members of the z-slab halo plan with a SELL-512-A or SELL-512 image.

@@ -16,7 +16,11 @@
  * with the fp32 image A~ as the inner operator. Per column, with
  * left = max(max_iter, 1) - 1 inner iterations to spend and s = 0:
  *   1. r_s = b - A x_s in fp64, rho_s = sqrt(r_s . r_s)
- *   2. stop if rho_s <= tolerance, or s == max_sweeps, or left == 0
+ *   2. stop if rho_s <= tolerance, or rho_s is not finite (NaN, inf), or
+ *      rho_s == 0.0 (whatever the tolerance, a negative one too), or
+ *      s == max_sweeps, or left == 0. There is no further sweep: normr is that
+ *      rho_s and x is x_s as it stands -- at s = 0 the caller's x0 bit for bit,
+ *      the signs of its zeros included
  *   3. the CG recurrence (HPCCG.cpp:312-402) on A~ d = r_s from d = 0, stopped
  *      at max(tolerance, inner_rtol * rho_s) or after left iterations (it_s)
  *   4. x_{s+1} = x_s + d, left -= it_s, s += 1
@@ -31,7 +35,21 @@
  *
  * Every column is independent: column c of a multi-column call is bitwise the
  * single-column call on it. A column that has stopped is frozen while the
- * others go on. Non-finite entries in B or X0 are not covered.
+ * others go on.
+ *
+ * Degenerate and non-finite columns (tests/test_gpu_columns_edge.py). An exact
+ * matrix: the column has hpccg_hip_solve_device's outcome -- a zero initial
+ * residual, a NaN in b or x0 or an infinite x0 entry: niters 0, normr 0.0 (NaN
+ * for the non-finite ones), x untouched; a negative tolerance from a zero
+ * residual or an infinite b entry: the reference's 0/0 path, niters 2, normr
+ * NaN, every x NaN. The refinement does NOT take the reference's NaN path: by
+ * step 2 each of these columns ends at its first residual step with niters 0,
+ * no sweep (resid has its one entry), normr rho_0 (0.0, NaN or inf) and x0
+ * returned bit for bit -- where the fp64 single solve returns niters 2 and a
+ * NaN x for an infinite b entry or a negative tolerance, the refinement
+ * returns niters 0 and x0. Either way the other columns of the call are
+ * bitwise unaffected, and nothing of a bad column stays in the workspace: the
+ * next call and hpccg_hip_mixed_sparsemv give their usual bits.
  *
  * Values outside fp32 range: a stored value whose fp32 image is not finite, or
  * that is nonzero with |v| < FLT_MIN, makes every mixed call on that matrix

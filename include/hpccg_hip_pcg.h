@@ -25,8 +25,16 @@
  *
  * Scope: one rank. Matrices of a communicator with more than one rank,
  * members of an in-process group and matrices with halo rows are refused with
- * HPCCG_HIP_EINVAL (message in hpccg_hip_last_error()). Non-finite entries in
- * B or X0 are not covered.
+ * HPCCG_HIP_EINVAL (message in hpccg_hip_last_error()).
+ *
+ * Degenerate and non-finite columns (tests/test_gpu_columns_edge.py): the
+ * recurrence above is taken literally, for any m. A zero initial residual, a
+ * NaN in b or x0, or an infinite x0 entry (p = x + 0.0*x is NaN there) runs no
+ * iteration: niters 0, normr 0.0 (NaN for the non-finite ones), x untouched. A
+ * negative tolerance from a zero residual, or an infinite b entry, takes the
+ * 0/0 path: niters 2, normr NaN, every x NaN. With m = 1.0 that is
+ * hpccg_hip_solve_device's outcome. The other columns of the call are bitwise
+ * unaffected, and nothing of a bad column stays in the workspace.
  *
  * Layout: B and X are column-major, column c at B + c * ldb (doubles), with
  * ldb, ldx >= nrow; the columns are copied into an aligned, padded workspace

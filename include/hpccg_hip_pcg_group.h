@@ -25,6 +25,13 @@
  * column c -- every member's x, niters, normr and the trace -- is bitwise
  * hpccg_hip_group_solve of that column alone on the same members.
  *
+ * A degenerate or non-finite column has the outcome written in hpccg_hip_pcg.h
+ * on every member (niters 0 with x untouched, or niters 2 with every x NaN),
+ * also where the bad entry lies on a plane a neighbour reads, with the halo
+ * kernel and with the halo by copies; the other columns are bitwise
+ * unaffected, and nothing of it stays in the members' workspaces
+ * (tests/test_gpu_columns_edge.py).
+ *
  * Scope: the whole group in rank order (Ms[r] is member r, nranks the group's
  * size), members of the z-slab halo plan with a SELL-512-A or SELL-512 image;
  * one device has been tested. Refused before any device work, the caller's X

@@ -134,9 +134,9 @@ def pcg_solve(hp, gpu, M, B, X0, max_iter, tol=0.0, minv=None, ld=None):
 # fixed-order (sequential) float64 dot. trace[k] is the normr iteration k
 # reports, sqrt(rr_{k-1}) (HPCCG.cpp:358), as in every solver here.
 # ---------------------------------------------------------------------------
-def restated(A, b, minv, max_iter, tol=0.0):
+def restated(A, b, minv, max_iter, tol=0.0, x0=None):
     with np.errstate(all="ignore"):
-        x = np.zeros(A.nrow)
+        x = np.zeros(A.nrow) if x0 is None else np.array(x0, np.float64)
         p = x + 0.0 * x
         Ap = oracle.sparsemv(A, p)
         r = b + (-1.0) * Ap

@@ -312,6 +312,55 @@ def pcg_group_lib() -> C.CDLL:
     return L
 
 
+POLY_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_poly.so")
+_poly_lib = None
+
+
+def poly_lib() -> C.CDLL:
+    """Load libhpccg_hip_poly.so (include/hpccg_hip_poly.h) on first use. It is
+    linked against libhpccg_hip.so beside it, so lib() is loaded first and both
+    share one copy of the main library."""
+    global _poly_lib
+    if _poly_lib is not None:
+        return _poly_lib
+    if os.environ.get("HPCCG_HIP_LIB", LIB_PATH) != LIB_PATH:
+        raise HPCCGError("the poly library runs on the in-tree libhpccg_hip.so only (HPCCG_HIP_LIB is set)")
+    lib()
+    if not os.path.exists(POLY_LIB_PATH):
+        raise HPCCGError(f"{POLY_LIB_PATH} missing: run build() (the polynomial solve has no fallback)")
+    try:
+        L = C.CDLL(POLY_LIB_PATH)
+    except OSError as e:
+        raise HPCCGError(f"{POLY_LIB_PATH} does not load: {e}") from e
+    vp, ip, dp, lp = C.c_void_p, C.c_int, C.c_double, C.c_longlong
+    PI, PD = C.POINTER(C.c_int), C.POINTER(C.c_double)
+    sig = {
+        "hpccg_hip_poly_abi_version": (ip, []),
+        "hpccg_hip_poly_solve_device": (ip, [vp, ip, vp, lp, vp, lp, vp, ip, dp, dp, ip, dp, PI, PD, PD]),
+        "hpccg_hip_poly_solve": (ip, [vp, ip, vp, lp, vp, lp, vp, ip, dp, dp, ip, dp, PI, PD, PD]),
+        "hpccg_hip_poly_bound": (ip, [vp, vp, PD]),
+        "hpccg_hip_poly_last_spectrum": (ip, [vp, PD, PD]),
+        "hpccg_hip_poly_last_trace": (ip, [vp, ip, PD, ip]),
+        "hpccg_hip_poly_release": (ip, [vp]),
+        "hpccg_hip_poly_workspace_bytes": (ip, [vp, C.POINTER(lp)]),
+        "hpccg_hip_poly_live_workspaces": (ip, [PI]),
+    }
+    for name, (res, args) in sig.items():
+        f = getattr(L, name)
+        f.restype = res
+        f.argtypes = args
+    _poly_lib = L
+    return L
+
+
+def poly_exported_symbols() -> list[str]:
+    """Functions include/hpccg_hip_poly.h declares (checked by the CPU suite)."""
+    import re
+    with open(os.path.join(ROOT, "include", "hpccg_hip_poly.h")) as f:
+        text = f.read()
+    return sorted(set(re.findall(r"\b(hpccg_hip_poly_\w+)\s*\(", text)))
+
+
 def group_pcg_exported_symbols() -> list[str]:
     """Functions include/hpccg_hip_pcg_group.h declares (checked by the CPU suite)."""
     import re
@@ -687,6 +736,32 @@ class Matrix:
         _check(_pcg_lib.hpccg_hip_pcg_workspace_bytes(self.h, C.byref(v)), "pcg_workspace_bytes")
         return v.value
 
+    def last_trace_poly(self, col: int, cap: int = 100000) -> np.ndarray:
+        """Residual trace (norm of r) of column col of the last HPCCG_poly on this matrix."""
+        out = np.zeros(cap, np.float64)
+        n = poly_lib().hpccg_hip_poly_last_trace(self.h, int(col), out.ctypes.data_as(C.POINTER(C.c_double)), cap)
+        if n < 0:
+            _check(n, "last_trace_poly")
+        return out[:n]
+
+    def last_spectrum_poly(self) -> tuple:
+        """(lmin, lmax) the last HPCCG_poly on this matrix used."""
+        lo, hi = C.c_double(0.0), C.c_double(0.0)
+        _check(poly_lib().hpccg_hip_poly_last_spectrum(self.h, C.byref(lo), C.byref(hi)), "last_spectrum_poly")
+        return lo.value, hi.value
+
+    def poly_release(self) -> None:
+        """Free this matrix's poly workspace (with its cached 1 / a_ii and bound) now (close() does it too)."""
+        if self.h and _poly_lib is not None:
+            _check(_poly_lib.hpccg_hip_poly_release(self.h), "poly_release")
+
+    def poly_workspace_bytes(self) -> int:
+        if _poly_lib is None:
+            return 0
+        v = C.c_longlong(0)
+        _check(_poly_lib.hpccg_hip_poly_workspace_bytes(self.h, C.byref(v)), "poly_workspace_bytes")
+        return v.value
+
     def close(self):
         # (a batch workspace goes with the matrix: the library's destroy hook,
         # whether or not the batch library was ever loaded)
@@ -916,6 +991,71 @@ def pcg_live_workspaces() -> int:
         return 0
     c = C.c_int(0)
     _check(_pcg_lib.hpccg_hip_pcg_live_workspaces(C.byref(c)), "pcg_live_workspaces")
+    return c.value
+
+
+# ---------------------------------------------------------------------------
+# Chebyshev polynomial preconditioned solve (include/hpccg_hip_poly.h)
+# ---------------------------------------------------------------------------
+def _minv_ptr(M: Matrix, minv, device):
+    """(pointer, keep-alive) of a caller's m: nrow entries, host or device."""
+    nrow = int(M.info()["nrow"])
+    if device:
+        if not isinstance(minv, int) and (minv.dim() != 1 or minv.shape[0] < nrow or
+                                          (minv.shape[0] > 1 and minv.stride(0) != 1)):
+            raise HPCCGError(f"minv: a contiguous 1-D tensor of {nrow} entries")
+        return _ptr(minv), minv
+    keep = np.ascontiguousarray(minv, np.float64)
+    if keep.ndim != 1 or keep.shape[0] < nrow:
+        raise HPCCGError(f"minv: a 1-D array of {nrow} entries")
+    return keep.ctypes.data, keep
+
+
+def HPCCG_poly(M: Matrix, B, X, degree: int = 2, lmin=None, lmax=None, minv=None, device=False, max_iter: int = 500,
+               tolerance: float = 0.0, nrhs=None, ldb=None, ldx=None):
+    """nrhs CG solves against M preconditioned by the Chebyshev polynomial of
+    `degree` steps in diag(minv) A on [lmin, lmax] (hpccg_hip_poly_solve[_device]);
+    minv None is Jacobi, lmax None the symmetric Gershgorin bound, lmin None
+    lmax / 30. Degree 0 is HPCCG_pcg bit for bit. A caller's bounds are not
+    verified. The loop test, niters and normr are on the 2-norm of r, as in
+    HPCCG. B, X, minv: as HPCCG_pcg. X is updated in place. Returns
+    (ierr, niters[nrhs], normr[nrhs], times)."""
+    L = poly_lib()
+    B, X = _one_column(B, "B"), _one_column(X, "X")
+    bp, nb, ldb_ = _cols(B, nrhs, ldb, "B")
+    xp, nx_, ldx_ = _cols(X, nrhs, ldx, "X")
+    if nb != nx_:
+        raise HPCCGError(f"B holds {nb} columns, X {nx_}")
+    if not device and not (isinstance(B, np.ndarray) and isinstance(X, np.ndarray)):
+        raise HPCCGError("host solve: B and X are numpy arrays")
+    mp, keep = (None, None) if minv is None else _minv_ptr(M, minv, device)
+    it = np.zeros(max(nb, 1), np.int32)
+    nr = np.zeros(max(nb, 1), np.float64)
+    times = np.zeros(7, np.float64)
+    f = L.hpccg_hip_poly_solve_device if device else L.hpccg_hip_poly_solve
+    rc = f(M.h, nb, bp, ldb_, xp, ldx_, mp, int(degree), 0.0 if lmin is None else float(lmin),
+           0.0 if lmax is None else float(lmax), max_iter, tolerance, it.ctypes.data_as(C.POINTER(C.c_int)),
+           nr.ctypes.data_as(C.POINTER(C.c_double)), times.ctypes.data_as(C.POINTER(C.c_double)))
+    _check(rc, "HPCCG_poly")
+    return rc, it[:nb], nr[:nb], times
+
+
+def poly_bound(M: Matrix, minv=None) -> float:
+    """The symmetric Gershgorin bound on the spectrum of diag(minv) A that
+    HPCCG_poly takes for lmax; minv: a device tensor / pointer of nrow entries,
+    or None for Jacobi."""
+    mp, keep = (None, None) if minv is None else _minv_ptr(M, minv, True)
+    v = C.c_double(0.0)
+    _check(poly_lib().hpccg_hip_poly_bound(M.h, mp, C.byref(v)), "poly_bound")
+    return v.value
+
+
+def poly_live_workspaces() -> int:
+    """Matrices that hold a poly workspace (0 when the library was never loaded)."""
+    if _poly_lib is None:
+        return 0
+    c = C.c_int(0)
+    _check(_poly_lib.hpccg_hip_poly_live_workspaces(C.byref(c)), "poly_live_workspaces")
     return c.value
 
 

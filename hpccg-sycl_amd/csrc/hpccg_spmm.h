@@ -1,13 +1,17 @@
 // hpccg_spmm.h -- the fp64 SpMM loops shared by the units that stream the
 // matrix's own fp64 image for several columns (hpccg_batch.hip,
-// hpccg_pcg.hip): the slot loop and the x-triple plan over SELL-512-A, the
-// int32-column loop over SELL-512, and the two kernel bodies around them. A
+// hpccg_pcg.hip, hpccg_pcg_group.hip, hpccg_poly.hip): the slot loop and the
+// x-triple plan over SELL-512-A, the int32-column loop over SELL-512, and the
+// two kernel bodies around them. A
 // unit's __global__ entry points are thin wrappers over the bodies (their
 // launch bounds and occupancy are the wrapper's); the bodies are templates on
 // the unit's argument struct A, a ColArgs with
 //   int tri;             width 27: slices whose offsets come in runs of three use the x-triple plan
 //   const double* aval;  the SELL-512-A values
 //   const double* vals;  the SELL-512 values
+// and on an ends policy E (SpmmToAp by default): where column 0's x lives and
+// what becomes of the row sums (hpccg_poly.hip's steps read z and apply the
+// Chebyshev step in registers).
 // Internal linkage (each unit compiles its own copy), like hpccg_columns.h.
 #pragma once
 #include "hpccg_columns.h"
@@ -105,8 +109,24 @@ __device__ __forceinline__ void arm()
     asm volatile("; value loads, arm %0" ::"n"(kArm));
 }
 
+// The default ends of a body: x is p, the row sums go to Ap with the p.Ap
+// slice partial (spmm_rows_out).
+struct SpmmToAp {
+    template <class A>
+    static __device__ __forceinline__ const double* x(const A& a)
+    {
+        return a.p;
+    }
+    template <int kR, class A>
+    static __device__ __forceinline__ void out(const A& a, bool prologue, int s, int row, const bool (&act)[kR],
+                                               const double (&sum)[kR][kRpt])
+    {
+        spmm_rows_out<kR>(a, prologue, s, row, act, sum);
+    }
+};
+
 // The body of a unit's SELL-512-A SpMM kernel<kW, kR> (one block per slice).
-template <int kW, int kR, class A>
+template <int kW, int kR, class A, class E = SpmmToAp>
 __device__ __forceinline__ void spmm_a_body(const A& a, bool prologue)
 {
     const int s = xcd_slice(a.grid);
@@ -118,7 +138,7 @@ __device__ __forceinline__ void spmm_a_body(const A& a, bool prologue)
     const double* __restrict__ vp = a.aval + vb * kSliceRows + (size_t)threadIdx.x * kRpt;
     const int* __restrict__ off = a.aoff + (size_t)s * kAMax;
     const int row = s * kSliceRows + threadIdx.x * kRpt;
-    const double* __restrict__ xr = a.p + (size_t)a.c0 * a.pcs + row;  // column c0 + c: x of column row + off at xr[c * pcs + off]
+    const double* __restrict__ xr = E::x(a) + (size_t)a.c0 * a.pcs + row;  // column c0 + c: x of column row + off at xr[c * pcs + off]
     double sum[kR][kRpt];
 #pragma unroll
     for (int c = 0; c < kR; c++)
@@ -161,7 +181,7 @@ __device__ __forceinline__ void spmm_a_body(const A& a, bool prologue)
     } else {
         spmm_a_slots<kW, kR, false, false>(a, vp, off, wdt, xr, act, sum);
     }
-    spmm_rows_out<kR>(a, prologue, s, row, act, sum);
+    E::template out<kR>(a, prologue, s, row, act, sum);
 }
 
 // ---------------------------------------------------------------------------
@@ -169,7 +189,7 @@ __device__ __forceinline__ void spmm_a_body(const A& a, bool prologue)
 // loop, x gathered from p_c. Padding slots (column -1, value 0) add +0. The
 // body of a unit's SELL-512 SpMM kernel<kR>.
 // ---------------------------------------------------------------------------
-template <int kR, class A>
+template <int kR, class A, class E = SpmmToAp>
 __device__ __forceinline__ void spmm_sell_body(const A& a, bool prologue)
 {
     const int s = xcd_slice(a.grid);
@@ -180,7 +200,7 @@ __device__ __forceinline__ void spmm_sell_body(const A& a, bool prologue)
     const int w = (int)(sld(a.slice_base + s + 1) - sld(a.slice_base + s));
     const double* __restrict__ vp = a.vals + base;
     const int* __restrict__ cp = a.cols + base;
-    const double* __restrict__ x0 = a.p + ((long long)a.c0 * a.pcs + a.xsell);
+    const double* __restrict__ x0 = E::x(a) + ((long long)a.c0 * a.pcs + a.xsell);
     double sum[kR][kRpt];
 #pragma unroll
     for (int c = 0; c < kR; c++)
@@ -204,7 +224,7 @@ __device__ __forceinline__ void spmm_sell_body(const A& a, bool prologue)
         }
     }
     const int row = s * kSliceRows + threadIdx.x * kRpt;
-    spmm_rows_out<kR>(a, prologue, s, row, act, sum);
+    E::template out<kR>(a, prologue, s, row, act, sum);
 }
 
 }  // namespace

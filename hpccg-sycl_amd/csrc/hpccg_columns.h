@@ -7,14 +7,17 @@
 // forms are the diagonally preconditioned recurrence (hpccg_pcg.hip): the same
 // statements with z = m r in r's place where the recurrence asks for z, and a
 // second dot, r.z, beside r.r; with m = 1 they are the plain ones bit for bit.
-//   device  ColState, ColArgs; the bodies of the p update, the SpMM epilogue,
-//           the update with its r.r slice partial and the finalize. A unit's
-//           __global__ entry points are thin wrappers over them; its SpMM loops
-//           (value type, load shape: the tuned part) are its own or
-//           hpccg_spmm.h's.
+//   device  ColState, ColArgs; the bodies of the init kernel, the p update, the
+//           SpMM epilogue, the update with its r.r slice partial and the
+//           finalize. A unit's __global__ entry points are thin wrappers over
+//           them; its SpMM loops (value type, load shape: the tuned part) are
+//           its own or hpccg_spmm.h's.
 //   host    error helpers, the workspace registry, the shared vector set with
-//           its grow-or-keep logic, the eager launch loop of one recurrence and
-//           the history -> trace read-back.
+//           its grow-or-keep logic, the eager launch loop of one recurrence,
+//           its end (wall time, the history -> trace read-back) and the trace's
+//           copy-out.
+// The same recurrence over an in-process rank group is hpccg_group.h, on top of
+// this header.
 // Internal linkage (each unit compiles its own copy), like hpccg_device.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -116,6 +119,23 @@ __device__ __forceinline__ bool active_cols(const ColArgs& a, bool (&act)[kR], b
 __device__ __forceinline__ double* slice_partials(const ColArgs& a, int which, int c)
 {
     return a.partial + ((size_t)which * a.cap + c) * (size_t)a.nslices;
+}
+
+// Every column of the call runs, with the call's tolerance and limit (one
+// thread per column).
+__device__ __forceinline__ void col_init(const ColArgs& a, int max_iter, double tol)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c == 0) *a.ended = 0;
+    if (c >= a.nrhs) return;
+    ColState s;
+    s.rtrans = s.oldrtrans = s.rr = s.pap = s.alpha = s.beta = 0.0;
+    s.tol = tol;
+    s.k = 0;
+    s.run = 1;
+    s.niters = 0;
+    s.max_iter = max_iter;
+    a.st[c] = s;
 }
 
 // ---------------------------------------------------------------------------
@@ -424,6 +444,12 @@ struct ColWorkspace {
     long long bytes = 0;  // of the vectors
 };
 
+// A workspace whose recurrences' normr traces are kept for the unit's
+// last_trace call (the mixed unit keeps its own records).
+struct TraceWorkspace : ColWorkspace {
+    std::vector<std::vector<double>> trace;  // per column of the last solve
+};
+
 template <class T>
 int alloc_zero(ColWorkspace* w, T** p, size_t count)
 {
@@ -676,6 +702,37 @@ int column_trace(const ColState& st, const double* h, std::vector<double>* tr)
     tr->push_back(std::sqrt(h[0]));
     for (int k = 1; k <= it; k++) tr->push_back(std::sqrt(h[k - 1]));
     return it;
+}
+
+// The end of the recurrences on w's stream, after the last launch: their wall
+// time since ev0, then every column's iterations, final normr and trace.
+// (inline, as copy_trace: a unit with records of its own uses neither)
+inline int finish_recurrence(TraceWorkspace* w, int nrhs, int* niters, double* normr, double* wall)
+{
+    HIP_TRY(hipEventRecord(w->ev1, w->v.stream));
+    std::vector<ColState> st;
+    std::vector<double> hist;
+    TRY(read_columns(w, nrhs, &st, &hist));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, w->ev0, w->ev1));
+    if (wall) *wall = 1e-3 * ms;
+    w->trace.assign(nrhs, {});
+    for (int c = 0; c < nrhs; c++) {
+        niters[c] = column_trace(st[c], hist.data() + (size_t)c * (size_t)w->hstride, &w->trace[c]);
+        normr[c] = w->trace[c][niters[c]];
+    }
+    return 0;
+}
+
+// The first cap entries of column col's trace into out: their number, or -1
+// where the last solve kept no such column (w: the matrix's record, if any).
+inline int copy_trace(const TraceWorkspace* w, int col, double* out, int cap)
+{
+    if (!w || col < 0 || col >= (int)w->trace.size()) return -1;
+    const std::vector<double>& tr = w->trace[col];
+    const int n = std::min<int>(std::max(cap, 0), (int)tr.size());
+    for (int i = 0; i < n; i++) out[i] = tr[i];
+    return n;
 }
 
 }  // namespace

@@ -68,17 +68,7 @@ struct PolyArgs : ColArgs {
 // Every column of the call runs, with the call's tolerance and limit.
 __global__ void k_poly_init(PolyArgs a, int max_iter, double tol)
 {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c == 0) *a.ended = 0;
-    if (c >= a.nrhs) return;
-    ColState s;
-    s.rtrans = s.oldrtrans = s.rr = s.pap = s.alpha = s.beta = 0.0;
-    s.tol = tol;
-    s.k = 0;
-    s.run = 1;
-    s.niters = 0;
-    s.max_iter = max_iter;
-    a.st[c] = s;
+    col_init(a, max_iter, tol);
 }
 
 // kPre: p = m r + beta p (degree 0). Else a.r is the stored z (degree >= 1):
@@ -327,7 +317,7 @@ __global__ __launch_bounds__(kBlock) void k_poly_bound_top(const double* __restr
 // ---------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------
-struct Workspace : ColWorkspace, JacobiCache {
+struct Workspace : TraceWorkspace, JacobiCache {
     double *r = nullptr, *x = nullptr, *b = nullptr;
     double *dd = nullptr, *zbuf = nullptr;  // zbuf: two sets of cap columns in p's layout
     // the bound's vectors (kept while the columns grow, counted in rest_bytes)
@@ -339,7 +329,6 @@ struct Workspace : ColWorkspace, JacobiCache {
     double cheb0 = 0.0, aj[kPolyMaxDegree + 1] = {}, bj[kPolyMaxDegree + 1] = {};
     bool solved = false;
     double last_lmin = 0.0, last_lmax = 0.0;
-    std::vector<std::vector<double>> trace;  // per column of the last solve
 
     Workspace() { ndots = 3; }
 
@@ -612,19 +601,7 @@ int run_cg(Workspace* w, int nrhs, const double* m, int max_iter, double tol, in
     HIP_TRY(hipEventRecord(w->ev0, s));
     hipLaunchKernelGGL(k_poly_init, dim3((nrhs + 63) / 64), dim3(64), 0, s, a, max_iter, tol);
     TRY(run_recurrence(w, a, nrhs, max_iter, launch_p, launch_spmm, launch_update, launch_finalize));
-    HIP_TRY(hipEventRecord(w->ev1, s));
-    std::vector<ColState> st;
-    std::vector<double> hist;
-    TRY(read_columns(w, nrhs, &st, &hist));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, w->ev0, w->ev1));
-    *wall = 1e-3 * ms;
-    w->trace.assign(nrhs, {});
-    for (int c = 0; c < nrhs; c++) {
-        niters[c] = column_trace(st[c], hist.data() + (size_t)c * (size_t)w->hstride, &w->trace[c]);
-        normr[c] = w->trace[c][niters[c]];
-    }
-    return 0;
+    return finish_recurrence(w, nrhs, niters, normr, wall);
 }
 
 // A caller's bounds: each finite and >= 0 (0.0: the default); both given, lmin < lmax.
@@ -771,12 +748,10 @@ int hpccg_hip_poly_last_trace(const hpccg_hip_matrix* M, int col, double* out, i
 {
     if (!M || !out) return fail(HPCCG_HIP_EINVAL, "poly: NULL argument");
     const Workspace* w = g_ws<Workspace>.find(M);
-    if (!w || col < 0 || col >= (int)w->trace.size())
+    const int n = copy_trace(w, col, out, cap);
+    if (n < 0)
         return fail(HPCCG_HIP_EINVAL, "poly: no trace of column %d (the last polynomial solve had %d)", col,
                     w ? (int)w->trace.size() : 0);
-    const std::vector<double>& tr = w->trace[col];
-    const int n = std::min<int>(std::max(cap, 0), (int)tr.size());
-    for (int i = 0; i < n; i++) out[i] = tr[i];
     return n;
 }
 

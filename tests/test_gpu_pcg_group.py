@@ -9,7 +9,9 @@ rank order. All members share one device.
   2. Jacobi on S A S with S b, S powers of two: s_i x'_i is bitwise the x of
      Jacobi on A with b, on every member (the per-row m from each member's own
      image, both image forms);
-  3. the halo kernel against the halo by copies: the same bits;
+  3. the halo kernel against the halo by copies: the same bits; with m = 1 the
+     group batch on the same members (the other user of the group engine,
+     csrc/hpccg_group.h): the same bits;
   4. on matrices scaled by s_i = 10^u_i: the group's trace against the one-rank
      preconditioned solve of the global matrix and against the NumPy
      restatement below (they differ in the dots' summation order only);
@@ -391,6 +393,36 @@ def test_the_halo_kernel_equals_the_copies(hp, gpu, shape):
     assert kernel[0][1] > 0 and all(np.all(np.isfinite(x)) for x in kernel[0][0])
     assert_same(kernel, copies)
     assert_same(pcg_solve(hp, gpu, cs, B, X0, MAX_ITER), kernel)  # (the switch is the call's own)
+
+
+def batch_solve(hp, gpu, cs, B, X0, max_iter):
+    """pcg_solve's result of the group batch on the same members."""
+    Bd = [dev(gpu, a) for a in cs.split(B)]
+    Xd = [dev(gpu, a) for a in cs.split(X0)]
+    its, nrs, _ = hp.group_HPCCG_batch(cs.Ms, Bd, Xd, max_iter=max_iter)
+    X = [x.cpu().numpy() for x in Xd]
+    return [([x[c].copy() for x in X], int(its[c]), float(nrs[c]), hp.group_last_trace_batch(cs.Ms, c).copy())
+            for c in range(B.shape[0])]
+
+
+@pytest.mark.parametrize("shape", ["3x33x17x9", "csr3"])
+def test_both_users_of_the_group_engine_agree(hp, gpu, shape):
+    """The group batch and the group pcg run one group engine (halo, sum, launch
+    loop, read-back) with their own kernels; with m = 1 those compute the same
+    numbers, so every member's x, niters, normr and every column's trace are
+    the same bits. 7 columns: launches of 4 + 3 in both; 5: 4 + 1 here, 4 + 2
+    in the batch. The batch runs before and after the pcg on the same members."""
+    cs = case(hp, shape)
+    try:
+        for ncol in (7, 5):
+            B, X0 = columns(cs, ncol)
+            batch = batch_solve(hp, gpu, cs, B, X0, MAX_ITER)
+            assert batch[0][1] > 0 and all(np.all(np.isfinite(x)) and x.any() for x in batch[0][0])
+            assert_same(pcg_solve(hp, gpu, cs, B, X0, MAX_ITER, minv=1.0), batch)
+            assert_same(batch_solve(hp, gpu, cs, B, X0, MAX_ITER), batch)
+    finally:
+        for M in cs.Ms:
+            M.batch_release()
 
 
 # ---------------------------------------------------------------------------

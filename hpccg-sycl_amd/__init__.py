@@ -353,6 +353,54 @@ def poly_lib() -> C.CDLL:
     return L
 
 
+POLY_GROUP_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_poly_group.so")
+_poly_group_lib = None
+
+
+def poly_group_lib() -> C.CDLL:
+    """Load libhpccg_hip_poly_group.so (include/hpccg_hip_poly_group.h) on first
+    use. It is linked against libhpccg_hip.so beside it, so lib() is loaded
+    first and both share one copy of the main library."""
+    global _poly_group_lib
+    if _poly_group_lib is not None:
+        return _poly_group_lib
+    if os.environ.get("HPCCG_HIP_LIB", LIB_PATH) != LIB_PATH:
+        raise HPCCGError("the group poly library runs on the in-tree libhpccg_hip.so only (HPCCG_HIP_LIB is set)")
+    lib()
+    if not os.path.exists(POLY_GROUP_LIB_PATH):
+        raise HPCCGError(f"{POLY_GROUP_LIB_PATH} missing: run build() (the group polynomial solve has no fallback)")
+    try:
+        L = C.CDLL(POLY_GROUP_LIB_PATH)
+    except OSError as e:
+        raise HPCCGError(f"{POLY_GROUP_LIB_PATH} does not load: {e}") from e
+    vp, ip, dp, lp = C.c_void_p, C.c_int, C.c_double, C.c_longlong
+    PI, PD, PV, PL = C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(vp), C.POINTER(lp)
+    sig = {
+        "hpccg_hip_group_poly_abi_version": (ip, []),
+        "hpccg_hip_group_poly_solve_device": (ip, [PV, ip, ip, PV, PL, PV, PL, PV, ip, dp, dp, ip, dp, PI, PD, PD]),
+        "hpccg_hip_group_poly_bound": (ip, [PV, ip, PV, PD]),
+        "hpccg_hip_group_poly_last_spectrum": (ip, [PV, ip, PD, PD]),
+        "hpccg_hip_group_poly_last_trace": (ip, [PV, ip, ip, PD, ip]),
+        "hpccg_hip_group_poly_release": (ip, [vp]),
+        "hpccg_hip_group_poly_workspace_bytes": (ip, [vp, PL]),
+        "hpccg_hip_group_poly_live_workspaces": (ip, [PI]),
+    }
+    for name, (res, args) in sig.items():
+        f = getattr(L, name)
+        f.restype = res
+        f.argtypes = args
+    _poly_group_lib = L
+    return L
+
+
+def group_poly_exported_symbols() -> list[str]:
+    """Functions include/hpccg_hip_poly_group.h declares (checked by the CPU suite)."""
+    import re
+    with open(os.path.join(ROOT, "include", "hpccg_hip_poly_group.h")) as f:
+        text = f.read()
+    return sorted(set(re.findall(r"\b(hpccg_hip_group_poly_\w+)\s*\(", text)))
+
+
 def poly_exported_symbols() -> list[str]:
     """Functions include/hpccg_hip_poly.h declares (checked by the CPU suite)."""
     import re
@@ -1286,6 +1334,138 @@ def group_pcg_live_workspaces() -> int:
         return 0
     c = C.c_int(0)
     _check(_pcg_group_lib.hpccg_hip_group_pcg_live_workspaces(C.byref(c)), "group_pcg_live_workspaces")
+    return c.value
+
+
+# ---------------------------------------------------------------------------
+# polynomial preconditioned solve over an in-process group (include/hpccg_hip_poly_group.h)
+# ---------------------------------------------------------------------------
+_POLY_HALO_COPIES_ENV = "HPCCG_GROUP_POLY_HALO_COPIES"
+
+
+def _group_minvs(Ms, minvs):
+    """The array of the members' device m pointers (None: Jacobi)."""
+    if minvs is None:
+        return None
+    P = len(Ms)
+    if len(minvs) != P:
+        raise HPCCGError(f"{P} members, {len(minvs)} minv vectors")
+    ptrs = []
+    for r, (M, m) in enumerate(zip(Ms, minvs)):
+        nrow = int(M.info()["nrow"])
+        if not isinstance(m, int) and (m.dim() != 1 or m.shape[0] < nrow or (m.shape[0] > 1 and m.stride(0) != 1)):
+            raise HPCCGError(f"minvs[{r}]: a contiguous 1-D tensor of {nrow} entries")
+        ptrs.append(_ptr(m))
+    return (C.c_void_p * P)(*ptrs)
+
+
+class _halo_copies_env:
+    """The library's halo-by-copies switch set (or cleared) for one call."""
+
+    def __init__(self, on):
+        self.on = on
+
+    def __enter__(self):
+        self.saved = os.environ.pop(_POLY_HALO_COPIES_ENV, None)
+        if self.on:
+            os.environ[_POLY_HALO_COPIES_ENV] = "1"
+
+    def __exit__(self, *exc):
+        os.environ.pop(_POLY_HALO_COPIES_ENV, None)
+        if self.saved is not None:
+            os.environ[_POLY_HALO_COPIES_ENV] = self.saved
+
+
+def group_HPCCG_poly(Ms: list, Bs, Xs, degree: int = 2, lmin=None, lmax=None, minvs=None, max_iter: int = 500,
+                     tolerance: float = 0.0, nrhs=None, ldb=None, ldx=None, halo_copies: bool = False):
+    """nrhs CG solves over an in-process group preconditioned by the Chebyshev
+    polynomial of `degree` steps in diag(minv) A on [lmin, lmax]
+    (hpccg_hip_group_poly_solve_device); minvs None is Jacobi, lmax None the
+    symmetric Gershgorin bound of the global matrix, lmin None lmax / 30. Degree
+    0 is group_HPCCG_pcg bit for bit; a group of one is HPCCG_poly bit for bit.
+    Bs, Xs, minvs: as group_HPCCG_pcg. Xs is updated in place. halo_copies
+    (diagnostic): move every ghost plane of z and p by one copy per column and
+    side instead of one kernel launch per member; the bits are the same.
+    Returns (niters[nrhs], normr[nrhs], times)."""
+    L = poly_group_lib()
+    P = len(Ms)
+    if len(Bs) != P or len(Xs) != P:
+        raise HPCCGError(f"{P} members, {len(Bs)} B and {len(Xs)} X column sets")
+    hs = (C.c_void_p * P)(*[M.h for M in Ms])
+    bp, nb, ldb_ = _group_cols(Bs, nrhs, ldb, "Bs")
+    xp, nx_, ldx_ = _group_cols(Xs, nrhs, ldx, "Xs")
+    if nb != nx_:
+        raise HPCCGError(f"Bs holds {nb} columns, Xs {nx_}")
+    mp = _group_minvs(Ms, minvs)
+    it = np.zeros(max(nb, 1), np.int32)
+    nr = np.zeros(max(nb, 1), np.float64)
+    times = np.zeros(7, np.float64)
+    with _halo_copies_env(halo_copies):
+        rc = L.hpccg_hip_group_poly_solve_device(hs, P, nb, bp, ldb_, xp, ldx_, mp, int(degree),
+                                                 0.0 if lmin is None else float(lmin),
+                                                 0.0 if lmax is None else float(lmax), max_iter, tolerance,
+                                                 it.ctypes.data_as(C.POINTER(C.c_int)),
+                                                 nr.ctypes.data_as(C.POINTER(C.c_double)),
+                                                 times.ctypes.data_as(C.POINTER(C.c_double)))
+    _check(rc, "group_HPCCG_poly")
+    return it[:nb], nr[:nb], times
+
+
+def group_poly_bound(Ms: list, minvs=None) -> float:
+    """The symmetric Gershgorin bound of the group's global matrix that
+    group_HPCCG_poly takes for lmax; minvs: per member a device tensor / pointer
+    of its nrow entries, or None for Jacobi."""
+    P = len(Ms)
+    hs = (C.c_void_p * P)(*[M.h for M in Ms])
+    v = C.c_double(0.0)
+    _check(poly_group_lib().hpccg_hip_group_poly_bound(hs, P, _group_minvs(Ms, minvs), C.byref(v)),
+           "group_poly_bound")
+    return v.value
+
+
+def group_last_trace_poly(Ms: list, col: int, cap: int = 100000) -> np.ndarray:
+    """Residual trace (norm of r) of column col of the last group_HPCCG_poly on Ms."""
+    P = len(Ms)
+    hs = (C.c_void_p * P)(*[M.h for M in Ms])
+    out = np.zeros(cap, np.float64)
+    n = poly_group_lib().hpccg_hip_group_poly_last_trace(hs, P, int(col), out.ctypes.data_as(C.POINTER(C.c_double)),
+                                                         cap)
+    if n < 0:
+        _check(n, "group_last_trace_poly")
+    return out[:n]
+
+
+def group_last_spectrum_poly(Ms: list) -> tuple:
+    """(lmin, lmax) the last group_HPCCG_poly on Ms used."""
+    P = len(Ms)
+    hs = (C.c_void_p * P)(*[M.h for M in Ms])
+    lo, hi = C.c_double(0.0), C.c_double(0.0)
+    _check(poly_group_lib().hpccg_hip_group_poly_last_spectrum(hs, P, C.byref(lo), C.byref(hi)),
+           "group_last_spectrum_poly")
+    return lo.value, hi.value
+
+
+def group_poly_workspace_bytes(M: Matrix) -> int:
+    """Device bytes member M's group poly workspace holds (0: none)."""
+    if _poly_group_lib is None:
+        return 0
+    v = C.c_longlong(0)
+    _check(_poly_group_lib.hpccg_hip_group_poly_workspace_bytes(M.h, C.byref(v)), "group_poly_workspace_bytes")
+    return v.value
+
+
+def group_poly_release(M: Matrix) -> None:
+    """Free member M's group poly workspace (with its caches) now (close() does it too)."""
+    if M.h and _poly_group_lib is not None:
+        _check(_poly_group_lib.hpccg_hip_group_poly_release(M.h), "group_poly_release")
+
+
+def group_poly_live_workspaces() -> int:
+    """Matrices that hold a group poly workspace (0 when the library was never loaded)."""
+    if _poly_group_lib is None:
+        return 0
+    c = C.c_int(0)
+    _check(_poly_group_lib.hpccg_hip_group_poly_live_workspaces(C.byref(c)), "group_poly_live_workspaces")
     return c.value
 
 

@@ -1,5 +1,6 @@
 // hpccg_columns.h -- the column-recurrence engine shared by the multi-column
-// units (hpccg_batch.hip, hpccg_mixed.hip, hpccg_pcg.hip, hpccg_pcg_group.hip, hpccg_poly.hip): one CG recurrence
+// units (hpccg_batch.hip, hpccg_mixed.hip, hpccg_pcg.hip, hpccg_pcg_group.hip, hpccg_poly.hip,
+// hpccg_poly_group.hip): one CG recurrence
 // per column of a call, each with the single solve's expressions and the
 // single solve's dot shape (hpccg_device.h). Every rounding-relevant expression
 // at column level and the loop test exist once, here, so column c of the batch

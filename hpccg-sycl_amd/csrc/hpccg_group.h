@@ -1,5 +1,6 @@
 // hpccg_group.h -- the column recurrence of hpccg_columns.h over an in-process
-// rank group, shared by the group solvers (hpccg_batch.hip, hpccg_pcg_group.hip).
+// rank group, shared by the group solvers (hpccg_batch.hip, hpccg_pcg_group.hip,
+// hpccg_poly_group.hip).
 // Member r is rank r of a z-slab job: it runs its unit's kernels on its own
 // rows, on its own stream, in a workspace of its own; the ghost planes of every
 // column's p move between the members after the p update, each member's
@@ -10,8 +11,10 @@
 //   device  GroupTotals and the body of the sum kernel; HaloArgs and the body
 //           of the halo kernel. The __global__ entry points are the units'.
 //   host    Group, its checks, the guarded p column of a member, the members'
-//           events, the halo (by copies or by the unit's kernel), the sum, the
-//           launch loop of the group's recurrence and the staging of B and X.
+//           events, the halo of any guarded column buffer (by copies or by the
+//           unit's kernel), the sum, the launch loop of the group's recurrence
+//           with its hook for a unit's own update phase, and the staging of B
+//           and X.
 // A unit keeps what differs: its args and make_args, its Workspace's vectors,
 // its launch dispatch. Internal linkage, like hpccg_columns.h.
 #pragma once
@@ -233,18 +236,24 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) ==
 // A unit's launch of its halo kernel (halo_body) on a member's stream.
 using HaloLaunch = void (*)(hipStream_t, dim3 grid, const HaloArgs&);
 
-// The halo of every column's p (group_halo in hpccg_solver.cpp, per column):
-// member r's ghost_lo rows are member r - 1's last rows, its ghost_hi rows
-// (from local row n) member r + 1's first, moved on r's stream once the
-// neighbours' streams have stored them (their events): by one launch of the
-// unit's halo kernel, or (launch_halo null) by copies, one per column and side.
-// Frozen columns' planes move too (their p no longer changes: harmless).
-// p is one buffer per column, not a ring. A neighbour cannot overwrite its p
-// before it has been read here: its next p update follows the group sum of p.Ap
-// (in the prologue: of r.r) on its stream, that sum waits for every member's
-// SpMM, and each member's SpMM follows its halo on its own stream.
-template <class W, class A>
-int group_halo(const Group<W, A>& G, int nrhs, HaloLaunch launch_halo)
+// Column 0 of a guarded column buffer of a member (guarded_p_column's layout:
+// its local row 0) and the buffer's column stride.
+struct HaloBuf {
+    double* p;
+    long long cs;
+};
+
+// The halo of every column of one guarded column buffer per member, buf(r)
+// being member r's (group_halo in hpccg_solver.cpp, per column): member r's
+// ghost_lo rows are member r - 1's last rows, its ghost_hi rows (from local row
+// n) member r + 1's first, moved on r's stream once the neighbours' streams
+// have stored them (their events): by one launch of the unit's halo kernel, or
+// (launch_halo null) by copies, one per column and side. Frozen columns' planes
+// move too (their vectors no longer change: harmless). What keeps a neighbour
+// from overwriting its rows before they have been read here is the caller's to
+// argue (group_halo below: p; hpccg_poly_group.hip: the two z buffers).
+template <class W, class A, class Buf>
+int group_halo_of(const Group<W, A>& G, int nrhs, HaloLaunch launch_halo, Buf buf)
 {
     if (G.P == 1) return 0;
     for (int r = 0; r < G.P; r++) {
@@ -253,27 +262,27 @@ int group_halo(const Group<W, A>& G, int nrhs, HaloLaunch launch_halo)
     }
     for (int r = 0; r < G.P; r++) {
         const MatrixView& v = G.v[r];
-        const A& a = G.a[r];
+        const HaloBuf a = buf(r);
         const bool lo = r > 0 && v.ghost_lo, hi = r < G.P - 1 && v.ghost_hi;
         if (!lo && !hi) continue;
         TRY(use(G, r));
         HaloArgs h{};
-        h.dcs = a.pcs;
+        h.dcs = a.cs;
         if (lo) {
-            const A& l = G.a[r - 1];
+            const HaloBuf l = buf(r - 1);
             HIP_TRY(hipStreamWaitEvent(v.stream, G.w[r - 1]->evr, 0));
             h.cnt_lo = v.ghost_lo;
             h.dst_lo = a.p - v.ghost_lo;
-            h.src_lo = l.p + (l.n - v.ghost_lo);
-            h.scs_lo = l.pcs;
+            h.src_lo = l.p + (G.v[r - 1].n - v.ghost_lo);
+            h.scs_lo = l.cs;
         }
         if (hi) {
-            const A& u = G.a[r + 1];
+            const HaloBuf u = buf(r + 1);
             HIP_TRY(hipStreamWaitEvent(v.stream, G.w[r + 1]->evr, 0));
             h.cnt_hi = v.ghost_hi;
-            h.dst_hi = a.p + a.n;
+            h.dst_hi = a.p + v.n;
             h.src_hi = u.p;
-            h.scs_hi = u.pcs;
+            h.scs_hi = u.cs;
         }
         if (!launch_halo) {
             for (int c = 0; lo && c < nrhs; c++)
@@ -296,9 +305,24 @@ int group_halo(const Group<W, A>& G, int nrhs, HaloLaunch launch_halo)
     return 0;
 }
 
+// The halo of every column's p after the p update.
+// p is one buffer per column, not a ring. A neighbour cannot overwrite its p
+// before it has been read here: its next p update follows the group sum of p.Ap
+// (in the prologue: of r.r) on its stream, that sum waits for every member's
+// SpMM, and each member's SpMM follows its halo on its own stream.
+template <class W, class A>
+int group_halo(const Group<W, A>& G, int nrhs, HaloLaunch launch_halo)
+{
+    return group_halo_of(G, nrhs, launch_halo, [&](int r) { return HaloBuf{G.a[r].p, G.a[r].pcs}; });
+}
+
 // The launchers of a unit's kernels, as run_recurrence takes them, with those
 // of the group's own: init and sum (col_init's and col_group_sum's kernels, one
 // thread per column) and the halo kernel (null: the halo by copies).
+// update_group (may be null: every member launches `update`): the whole group's
+// update phase, for a unit whose update exchanges ghost planes of its own
+// between the members' launches (hpccg_poly_group.hip: the steps and the halos
+// of z); it leaves every member's update launched on its stream.
 template <class W, class A>
 struct GroupLaunch {
     void (*init)(const W*, const A&, int max_iter, double tol);
@@ -308,7 +332,20 @@ struct GroupLaunch {
     void (*finalize)(const W*, const A&, int which, int store_total);
     void (*sum)(const W*, const A&, const GroupTotals&, int which);
     HaloLaunch halo;
+    int (*update_group)(const Group<W, A>&, int nrhs, bool prologue, HaloLaunch halo) = nullptr;
 };
+
+// The update phase of every member, each on its own stream.
+template <class W, class A>
+int group_update(const Group<W, A>& G, int nrhs, bool prologue, const GroupLaunch<W, A>& L)
+{
+    if (L.update_group) return L.update_group(G, nrhs, prologue, L.halo);
+    for (int r = 0; r < G.P; r++) {
+        TRY(use(G, r));
+        L.update(G.w[r], G.a[r], prologue);
+    }
+    return 0;
+}
 
 // The global dots `which` of every running column and its state on every
 // member: member 0's stream waits for every member's local finalize, runs the
@@ -359,7 +396,10 @@ int group_run_cg(const Group<W, A>& G, int nrhs, int max_iter, double tol, const
     for (int r = 0; r < G.P; r++) {
         TRY(use(G, r));
         L.spmm(G.w[r], G.a[r], true);
-        L.update(G.w[r], G.a[r], true);
+    }
+    TRY(group_update(G, nrhs, true, L));
+    for (int r = 0; r < G.P; r++) {
+        TRY(use(G, r));
         L.finalize(G.w[r], G.a[r], kDotRR, 1);
     }
     TRY(group_sum(G, gt, kDotRR, L));
@@ -376,9 +416,9 @@ int group_run_cg(const Group<W, A>& G, int nrhs, int max_iter, double tol, const
             L.finalize(G.w[r], G.a[r], kDotPAP, 1);
         }
         TRY(group_sum(G, gt, kDotPAP, L));
+        TRY(group_update(G, nrhs, false, L));
         for (int r = 0; r < G.P; r++) {
             TRY(use(G, r));
-            L.update(G.w[r], G.a[r], false);
             L.finalize(G.w[r], G.a[r], kDotRR, 1);
         }
         TRY(group_sum(G, gt, kDotRR, L));

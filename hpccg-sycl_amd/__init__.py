@@ -393,6 +393,56 @@ def poly_group_lib() -> C.CDLL:
     return L
 
 
+POLY32_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_poly32.so")
+_poly32_lib = None
+
+
+def poly32_lib() -> C.CDLL:
+    """Load libhpccg_hip_poly32.so (include/hpccg_hip_poly32.h) on first use. It
+    is linked against libhpccg_hip.so beside it, so lib() is loaded first and
+    both share one copy of the main library."""
+    global _poly32_lib
+    if _poly32_lib is not None:
+        return _poly32_lib
+    if os.environ.get("HPCCG_HIP_LIB", LIB_PATH) != LIB_PATH:
+        raise HPCCGError("the poly32 library runs on the in-tree libhpccg_hip.so only (HPCCG_HIP_LIB is set)")
+    lib()
+    if not os.path.exists(POLY32_LIB_PATH):
+        raise HPCCGError(f"{POLY32_LIB_PATH} missing: run build() (the fp32-image polynomial solve has no fallback)")
+    try:
+        L = C.CDLL(POLY32_LIB_PATH)
+    except OSError as e:
+        raise HPCCGError(f"{POLY32_LIB_PATH} does not load: {e}") from e
+    vp, ip, dp, lp = C.c_void_p, C.c_int, C.c_double, C.c_longlong
+    PI, PD = C.POINTER(C.c_int), C.POINTER(C.c_double)
+    sig = {
+        "hpccg_hip_poly32_abi_version": (ip, []),
+        "hpccg_hip_poly32_solve_device": (ip, [vp, ip, vp, lp, vp, lp, vp, ip, dp, dp, ip, dp, PI, PD, PD]),
+        "hpccg_hip_poly32_solve": (ip, [vp, ip, vp, lp, vp, lp, vp, ip, dp, dp, ip, dp, PI, PD, PD]),
+        "hpccg_hip_poly32_bound": (ip, [vp, vp, PD]),
+        "hpccg_hip_poly32_last_spectrum": (ip, [vp, PD, PD]),
+        "hpccg_hip_poly32_last_trace": (ip, [vp, ip, PD, ip]),
+        "hpccg_hip_poly32_info": (ip, [vp, C.POINTER(lp)]),
+        "hpccg_hip_poly32_release": (ip, [vp]),
+        "hpccg_hip_poly32_workspace_bytes": (ip, [vp, C.POINTER(lp)]),
+        "hpccg_hip_poly32_live_workspaces": (ip, [PI]),
+    }
+    for name, (res, args) in sig.items():
+        f = getattr(L, name)
+        f.restype = res
+        f.argtypes = args
+    _poly32_lib = L
+    return L
+
+
+def poly32_exported_symbols() -> list[str]:
+    """Functions include/hpccg_hip_poly32.h declares (checked by the CPU suite)."""
+    import re
+    with open(os.path.join(ROOT, "include", "hpccg_hip_poly32.h")) as f:
+        text = f.read()
+    return sorted(set(re.findall(r"\b(hpccg_hip_poly32_\w+)\s*\(", text)))
+
+
 def group_poly_exported_symbols() -> list[str]:
     """Functions include/hpccg_hip_poly_group.h declares (checked by the CPU suite)."""
     import re
@@ -810,6 +860,32 @@ class Matrix:
         _check(_poly_lib.hpccg_hip_poly_workspace_bytes(self.h, C.byref(v)), "poly_workspace_bytes")
         return v.value
 
+    def last_trace_poly32(self, col: int, cap: int = 100000) -> np.ndarray:
+        """Residual trace (norm of r) of column col of the last HPCCG_poly32 on this matrix."""
+        out = np.zeros(cap, np.float64)
+        n = poly32_lib().hpccg_hip_poly32_last_trace(self.h, int(col), out.ctypes.data_as(C.POINTER(C.c_double)), cap)
+        if n < 0:
+            _check(n, "last_trace_poly32")
+        return out[:n]
+
+    def last_spectrum_poly32(self) -> tuple:
+        """(lmin, lmax) the last HPCCG_poly32 on this matrix used."""
+        lo, hi = C.c_double(0.0), C.c_double(0.0)
+        _check(poly32_lib().hpccg_hip_poly32_last_spectrum(self.h, C.byref(lo), C.byref(hi)), "last_spectrum_poly32")
+        return lo.value, hi.value
+
+    def poly32_release(self) -> None:
+        """Free this matrix's poly32 workspace and fp32 image now (close() does it too)."""
+        if self.h and _poly32_lib is not None:
+            _check(_poly32_lib.hpccg_hip_poly32_release(self.h), "poly32_release")
+
+    def poly32_workspace_bytes(self) -> int:
+        if _poly32_lib is None:
+            return 0
+        v = C.c_longlong(0)
+        _check(_poly32_lib.hpccg_hip_poly32_workspace_bytes(self.h, C.byref(v)), "poly32_workspace_bytes")
+        return v.value
+
     def close(self):
         # (a batch workspace goes with the matrix: the library's destroy hook,
         # whether or not the batch library was ever loaded)
@@ -1104,6 +1180,65 @@ def poly_live_workspaces() -> int:
         return 0
     c = C.c_int(0)
     _check(_poly_lib.hpccg_hip_poly_live_workspaces(C.byref(c)), "poly_live_workspaces")
+    return c.value
+
+
+# ---------------------------------------------------------------------------
+# the polynomial solve with its steps streamed from an fp32 matrix image
+# (include/hpccg_hip_poly32.h)
+# ---------------------------------------------------------------------------
+def HPCCG_poly32(M: Matrix, B, X, degree: int = 2, lmin=None, lmax=None, minv=None, device=False,
+                 max_iter: int = 500, tolerance: float = 0.0, nrhs=None, ldb=None, ldx=None):
+    """HPCCG_poly with the polynomial's steps reading an fp32 image of the
+    matrix values (hpccg_hip_poly32_solve[_device]); the system solved is the
+    fp64 one. Where the image is exact (poly32_info) every column is HPCCG_poly
+    bit for bit; degree 0 is HPCCG_pcg bit for bit on any matrix. A matrix
+    outside fp32 range is refused. Arguments and return: HPCCG_poly's."""
+    L = poly32_lib()
+    B, X = _one_column(B, "B"), _one_column(X, "X")
+    bp, nb, ldb_ = _cols(B, nrhs, ldb, "B")
+    xp, nx_, ldx_ = _cols(X, nrhs, ldx, "X")
+    if nb != nx_:
+        raise HPCCGError(f"B holds {nb} columns, X {nx_}")
+    if not device and not (isinstance(B, np.ndarray) and isinstance(X, np.ndarray)):
+        raise HPCCGError("host solve: B and X are numpy arrays")
+    mp, keep = (None, None) if minv is None else _minv_ptr(M, minv, device)
+    it = np.zeros(max(nb, 1), np.int32)
+    nr = np.zeros(max(nb, 1), np.float64)
+    times = np.zeros(7, np.float64)
+    f = L.hpccg_hip_poly32_solve_device if device else L.hpccg_hip_poly32_solve
+    rc = f(M.h, nb, bp, ldb_, xp, ldx_, mp, int(degree), 0.0 if lmin is None else float(lmin),
+           0.0 if lmax is None else float(lmax), max_iter, tolerance, it.ctypes.data_as(C.POINTER(C.c_int)),
+           nr.ctypes.data_as(C.POINTER(C.c_double)), times.ctypes.data_as(C.POINTER(C.c_double)))
+    _check(rc, "HPCCG_poly32")
+    return rc, it[:nb], nr[:nb], times
+
+
+def poly32_bound(M: Matrix, minv=None) -> float:
+    """The symmetric Gershgorin bound of the fp64 image that HPCCG_poly32 takes
+    for lmax (poly_bound's value); minv: a device tensor / pointer of nrow
+    entries, or None for Jacobi."""
+    mp, keep = (None, None) if minv is None else _minv_ptr(M, minv, True)
+    v = C.c_double(0.0)
+    _check(poly32_lib().hpccg_hip_poly32_bound(M.h, mp, C.byref(v)), "poly32_bound")
+    return v.value
+
+
+def poly32_info(M: Matrix) -> dict:
+    """The poly32 library's fp32 image of M (built on first use): exact (every
+    value survives double -> float -> double: HPCCG_poly32 is then HPCCG_poly
+    bit for bit), its device bytes, and the values that did not survive."""
+    a = (C.c_longlong * 4)()
+    _check(poly32_lib().hpccg_hip_poly32_info(M.h, a), "poly32_info")
+    return {"exact": int(a[0]), "image_bytes": int(a[1]), "inexact_values": int(a[2])}
+
+
+def poly32_live_workspaces() -> int:
+    """Matrices that hold a poly32 workspace (0 when the library was never loaded)."""
+    if _poly32_lib is None:
+        return 0
+    c = C.c_int(0)
+    _check(_poly32_lib.hpccg_hip_poly32_live_workspaces(C.byref(c)), "poly32_live_workspaces")
     return c.value
 
 

@@ -1,7 +1,7 @@
 // hpccg_jacobi.h -- the diagonal preconditioner's vector, shared by the
-// preconditioned units (hpccg_pcg.hip, hpccg_pcg_group.hip, hpccg_poly.hip,
-// hpccg_poly_group.hip): reading a_ii from
-// the matrix image, checking a caller's m, and the part of a workspace that
+// preconditioned units (hpccg_pcg.hip, hpccg_pcg_group.hip, and through
+// hpccg_poly_host.h hpccg_poly.hip, hpccg_poly32.hip, hpccg_poly_group.hip):
+// reading a_ii from the matrix image, checking a caller's m, and the part of a workspace that
 // holds them while its columns grow.
 //   device  the bodies of the diagonal kernel and of the check kernel; a unit's
 //           __global__ entry points are thin wrappers over them

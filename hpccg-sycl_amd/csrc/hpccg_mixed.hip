@@ -28,13 +28,14 @@
 //   residual  k_mixed_residual: r = b - A x from an fp64 A x with the r.r slice
 //             partials | x = x + d (refinement)
 // The recurrence itself -- the column's state, those bodies, the workspace
-// registry and the launch loop -- is hpccg_columns.h; this unit adds the fp32
-// image, its SpMM loops and the refinement. Every dot keeps the rounding shape
+// registry and the launch loop -- is hpccg_columns.h; the image -- its convert
+// body, its slot loops, its record and builder on the host -- is
+// hpccg_spmm32.h, shared with hpccg_poly32.hip. This unit adds the frames of
+// its two SpMM kernels and the refinement. Every dot keeps the rounding shape
 // of hpccg_device.h. No kernel here waits on another block.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -42,6 +43,7 @@
 
 #include "../../include/hpccg_hip_mixed.h"
 #include "hpccg_columns.h"
+#include "hpccg_spmm32.h"
 
 #pragma clang fp contract(off)
 
@@ -58,62 +60,12 @@ struct MixedArgs : ColArgs {
     const float* img;  // the fp32 values (layout above)
 };
 
-typedef float f4v __attribute__((ext_vector_type(4)));
-typedef float f2v __attribute__((ext_vector_type(2)));
-
-template <bool kNT>
-__device__ __forceinline__ f4v ld_f4(const float* __restrict__ p)
-{
-    if constexpr (kNT)
-        return __builtin_nontemporal_load(reinterpret_cast<const f4v*>(p));
-    else
-        return *reinterpret_cast<const f4v*>(p);
-}
-
-template <bool kNT>
-__device__ __forceinline__ f2v ld_f2(const float* __restrict__ p)
-{
-    if constexpr (kNT)
-        return __builtin_nontemporal_load(reinterpret_cast<const f2v*>(p));
-    else
-        return *reinterpret_cast<const f2v*>(p);
-}
-
-// ---------------------------------------------------------------------------
-// fp64 image -> fp32 image, one block per slice. width > 0: every slice has
-// that many slots (base s * width); else slice s holds base_tab[s] ..
-// base_tab[s + 1]. flags[0] counts the values with (double)(float)v != v,
-// flags[1] those outside fp32 range (image not finite, or nonzero below
-// FLT_MIN). Zero holes and padding slots are exact.
-// ---------------------------------------------------------------------------
+// fp64 image -> fp32 image with the two counts: hpccg_spmm32.h's body.
 __global__ __launch_bounds__(kBlock) void k_mixed_convert(const double* __restrict__ vals,
                                                           const unsigned int* __restrict__ base_tab, int width,
                                                           float* __restrict__ img, unsigned long long* flags)
 {
-    const int s = blockIdx.x;
-    const int w = width > 0 ? width : (int)(base_tab[s + 1] - base_tab[s]);
-    const size_t vb = (width > 0 ? (size_t)s * width : (size_t)base_tab[s]) * kSliceRows;
-    const double* __restrict__ src = vals + vb + (size_t)threadIdx.x * kRpt;
-    float* __restrict__ dst = img + vb;
-    const int wp = w & ~1;  // slots in pairs
-    unsigned int inexact = 0, range = 0;
-    for (int j = 0; j < w; j++) {
-        const Rows v = ld(src + (size_t)j * kSliceRows);
-        f2v f;
-        f.x = (float)v.v[0];
-        f.y = (float)v.v[1];
-#pragma unroll
-        for (int i = 0; i < kRpt; i++) {
-            const float fi = i ? f.y : f.x;
-            if (!((double)fi == v.v[i])) inexact++;
-            if (!isfinite(fi) || (v.v[i] != 0.0 && fabs(v.v[i]) < (double)FLT_MIN)) range++;
-        }
-        float* q = j < wp ? dst + (size_t)(j & ~1) * kSliceRows + (size_t)threadIdx.x * 4 + (j & 1) * 2
-                          : dst + (size_t)j * kSliceRows + (size_t)threadIdx.x * 2;
-        *reinterpret_cast<f2v*>(q) = f;
-    }
-    if (inexact) atomicAdd(flags, (unsigned long long)inexact);
-    if (range) atomicAdd(flags + 1, (unsigned long long)range);
+    convert32_body(vals, base_tab, width, img, flags);
 }
 
 template <int kR>
@@ -122,56 +74,20 @@ __global__ __launch_bounds__(kBlock) void k_mixed_p(MixedArgs a, bool prologue)
     col_p<kR>(a, prologue);
 }
 
-// One slot of the A image for every column: sum[c][i] = sum[c][i] +
-// (double)v[i] * x_c[row + off + i], the fp64 kernels' row-sum step.
-template <int kR, bool kAll>
-__device__ __forceinline__ void slot_a(const MixedArgs& a, float v0, float v1, int oj, const double* __restrict__ xr,
-                                       const bool (&act)[kR], double (&sum)[kR][kRpt])
-{
-    const double w0 = (double)v0, w1 = (double)v1;
-#pragma unroll
-    for (int c = 0; c < kR; c++) {
-        if (kAll || act[c]) {
-            const Rows xv = ld_u(xr + ((long long)c * a.pcs + oj));
-            sum[c][0] = sum[c][0] + w0 * xv.v[0];
-            sum[c][1] = sum[c][1] + w1 * xv.v[1];
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------
-// SpMM over the fp32 SELL-512-A image: k_batch_spmm_a's slot loop, two slots
-// per 16-B value load. Column c's x is p_c at the slice's offsets (holes: 0.0
-// times a finite word of p_c's zeroed guard zone or a real neighbour). Per row
-// and column the products are added in slot order with no contraction: the
-// fp64 kernels' row sum of the widened values.
-// ---------------------------------------------------------------------------
-template <int kW, int kR, bool kNT, bool kAll>
-__device__ __forceinline__ void spmm_a_slots(const MixedArgs& a, const float* __restrict__ base,
-                                             const int* __restrict__ off, int wdt, const double* __restrict__ xr,
-                                             const bool (&act)[kR], double (&sum)[kR][kRpt])
-{
-    const float* __restrict__ vp = base + (size_t)threadIdx.x * 4;
-    const int np = wdt >> 1;
-#pragma unroll kW > 0 ? kW / 2 : 2
-    for (int q = 0; q < np; q++) {
-        const f4v v = ld_f4<kNT>(vp + (size_t)(2 * q) * kSliceRows);
-        const int o0 = sld(off + 2 * q), o1 = sld(off + 2 * q + 1);
-        slot_a<kR, kAll>(a, v.x, v.y, o0, xr, act, sum);
-        slot_a<kR, kAll>(a, v.z, v.w, o1, xr, act, sum);
-    }
-    if (wdt & 1) {  // (block-uniform) the odd width's last slot
-        const f2v v = ld_f2<kNT>(base + (size_t)(wdt - 1) * kSliceRows + (size_t)threadIdx.x * 2);
-        slot_a<kR, kAll>(a, v.x, v.y, sld(off + wdt - 1), xr, act, sum);
-    }
-}
-
+// SpMM over the fp32 SELL-512-A image: hpccg_spmm32.h's slot loop (two slots
+// per 16-B value load) in this unit's own frame, without the x-triple plan
+// (this library's 27-wide four-column form is the plain slot loop). The frames
+// of the two SpMM kernels stay here: as wrappers over spmm32_a_body /
+// spmm32_sell_body the compiler lays out the four-column forms' address
+// arithmetic differently (profiles/poly_host_refactor/README.md).
 // kNT: the value loads are non-temporal. A template parameter of the kernel,
 // chosen on the host from the view's nt flag: as a branch inside the kernel
 // the two arms differ in the hint alone, the optimiser merges them and the
 // hint is lost (so it was with one column, where no other arm keeps them apart).
 // amdgpu_waves_per_eu(4): the register budget (at most 128 VGPRs; the batch
 // library's default), not a tuned target.
+// ---------------------------------------------------------------------------
 template <int kW, bool kNT, int kR>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) void k_mixed_spmm_a(MixedArgs a,
                                                                                                 bool prologue)
@@ -192,35 +108,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
 #pragma unroll
         for (int i = 0; i < kRpt; i++) sum[c][i] = 0.0;
     if (all)
-        spmm_a_slots<kW, kR, kNT, true>(a, base, off, wdt, xr, act, sum);
+        spmm32_a_slots<kW, kR, kNT, true>(a, base, off, wdt, xr, act, sum);
     else
-        spmm_a_slots<kW, kR, kNT, false>(a, base, off, wdt, xr, act, sum);
+        spmm32_a_slots<kW, kR, kNT, false>(a, base, off, wdt, xr, act, sum);
     spmm_rows_out<kR>(a, prologue, s, row, act, sum);
-}
-
-// One slot of the SELL-512 image for every column (k_batch_spmm_sell's step).
-template <int kR>
-__device__ __forceinline__ void slot_sell(const MixedArgs& a, float v0, float v1, int c0, int c1,
-                                          const double* __restrict__ x0, const bool (&act)[kR],
-                                          double (&sum)[kR][kRpt])
-{
-    const double w[kRpt] = {(double)v0, (double)v1};
-    const int col[kRpt] = {c0, c1};
-#pragma unroll
-    for (int c = 0; c < kR; c++) {
-        if (!act[c]) continue;  // (block-uniform)
-        const double* __restrict__ x = x0 + (size_t)c * a.pcs;
-#pragma unroll
-        for (int i = 0; i < kRpt; i++) {
-            const double xv = (col[i] >= 0) ? x[col[i]] : 0.0;
-            sum[c][i] = sum[c][i] + w[i] * xv;
-        }
-    }
 }
 
 // ---------------------------------------------------------------------------
 // SpMM over the fp32 SELL-512 image (the shared int32 columns; matrices
-// without an A image): k_batch_spmm_sell's loop. Padding slots (column -1,
+// without an A image): hpccg_spmm32.h's slot step. Padding slots (column -1,
 // value 0) add +0.
 // ---------------------------------------------------------------------------
 template <bool kNT, int kR>
@@ -247,13 +143,13 @@ __global__ __launch_bounds__(kBlock) void k_mixed_spmm_sell(MixedArgs a, bool pr
         const f4v v = ld_f4<kNT>(base + (size_t)(2 * q) * kSliceRows + (size_t)threadIdx.x * 4);
         const i2v ca = *reinterpret_cast<const i2v*>(cp + (size_t)(2 * q) * kSliceRows);
         const i2v cb = *reinterpret_cast<const i2v*>(cp + (size_t)(2 * q + 1) * kSliceRows);
-        slot_sell<kR>(a, v.x, v.y, ca.x, ca.y, x0, act, sum);
-        slot_sell<kR>(a, v.z, v.w, cb.x, cb.y, x0, act, sum);
+        slot32_sell<kR>(a, v.x, v.y, ca.x, ca.y, x0, act, sum);
+        slot32_sell<kR>(a, v.z, v.w, cb.x, cb.y, x0, act, sum);
     }
     if (w & 1) {  // (block-uniform) the odd width's last slot
         const f2v v = ld_f2<kNT>(base + (size_t)(w - 1) * kSliceRows + (size_t)threadIdx.x * 2);
         const i2v ca = *reinterpret_cast<const i2v*>(cp + (size_t)(w - 1) * kSliceRows);
-        slot_sell<kR>(a, v.x, v.y, ca.x, ca.y, x0, act, sum);
+        slot32_sell<kR>(a, v.x, v.y, ca.x, ca.y, x0, act, sum);
     }
     const int row = s * kSliceRows + threadIdx.x * kRpt;
     spmm_rows_out<kR>(a, prologue, s, row, act, sum);
@@ -318,12 +214,7 @@ struct ColRecord {
     std::vector<double> resid;  // rho_s, then the final residual
 };
 
-struct Workspace : ColWorkspace {
-    // the fp32 image
-    float* img = nullptr;
-    long long img_bytes = 0;
-    bool built = false;
-    long long inexact = 0, out_of_range = 0;
+struct Workspace : ColWorkspace, Image32 {
     // the vectors of its own
     bool refine = false;  // x, b are buffers of their own (the refinement's d, r_s)
     double *r = nullptr, *x = nullptr, *b = nullptr, *ox = nullptr, *ob = nullptr;
@@ -337,66 +228,13 @@ struct Workspace : ColWorkspace {
         r = x = b = ox = ob = nullptr;
         refine = false;
     }
-    void free_own_rest()
-    {
-        if (img) (void)hipFree(img);
-    }
+    void free_own_rest() { free_image(); }
 };
 
-int out_of_range(const Workspace* w)
-{
-    return fail(HPCCG_HIP_EINVAL,
-                "mixed: the matrix is outside fp32 range (%lld stored values with no finite, normal fp32 image)",
-                w->out_of_range);
-}
-
-// The fp32 image, built once per matrix on the device from the image it holds.
+// The fp32 image, built once per matrix (hpccg_spmm32.h).
 int ensure_image(Workspace* w)
 {
-    if (w->built) return w->out_of_range ? out_of_range(w) : 0;
-    const MatrixView& v = w->v;
-    hipStream_t s = v.stream;
-    HIP_TRY(hipSetDevice(v.device));
-    const double* vals = v.has_a ? v.aval : v.vals;
-    const unsigned int* tab = v.has_a ? v.abase : v.slice_base;
-    const int width = v.has_a ? v.a_width : 0;
-    long long slot_rows = (long long)v.nslices * width;
-    if (width <= 0) {
-        unsigned int last = 0;
-        HIP_TRY(hipMemcpyAsync(&last, tab + v.nslices, sizeof last, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        slot_rows = last;
-    }
-    const size_t bytes = sizeof(float) * (size_t)std::max<long long>(slot_rows, 1) * kSliceRows;
-    unsigned long long* flags = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w->img), bytes));
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&flags), 2 * sizeof *flags);
-    unsigned long long h[2] = {0, 0};
-    if (e == hipSuccess) e = hipMemsetAsync(flags, 0, 2 * sizeof *flags, s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_mixed_convert, dim3(v.nslices), dim3(kBlock), 0, s, vals, tab, width, w->img, flags);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(h, flags, sizeof h, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (flags) (void)hipFree(flags);
-    if (e != hipSuccess) {
-        (void)hipFree(w->img);
-        w->img = nullptr;
-        return fail(e == hipErrorOutOfMemory ? HPCCG_HIP_ENOMEM : HPCCG_HIP_EHIP, "mixed: building the fp32 image: %s",
-                    hipGetErrorString(e));
-    }
-    w->built = true;
-    w->inexact = (long long)h[0];
-    w->out_of_range = (long long)h[1];
-    w->img_bytes = (long long)bytes;
-    if (w->out_of_range) {  // never solved with: the image goes, the verdict stays
-        (void)hipFree(w->img);
-        w->img = nullptr;
-        w->img_bytes = 0;
-        return out_of_range(w);
-    }
-    return 0;
+    return ensure_image32(w, w->v, k_mixed_convert, "mixed");
 }
 
 // Room for ncols columns and a history of max_iter + 1 entries per column;

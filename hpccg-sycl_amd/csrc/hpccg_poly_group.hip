@@ -29,24 +29,20 @@
 // Degree 0 applies no polynomial: the launches are the group pcg's.
 //
 // The group engine is hpccg_group.h, shared with hpccg_batch.hip and
-// hpccg_pcg_group.hip; this unit adds its args, its launch dispatch, the
-// members' preconditioner and bound, and the update phase with the halos of z
-// (group_poly_update: the ordering argument is written there). Ordering between
+// hpccg_pcg_group.hip; the polynomial's workspace, arguments, launchers and
+// interval are hpccg_poly_host.h, shared with hpccg_poly.hip and
+// hpccg_poly32.hip. This unit adds the members' preconditioner and bound and
+// the update phase with the halos of z (group_poly_update: the ordering
+// argument is written there). Ordering between
 // the members is by stream events only. No kernel here waits on another block.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cmath>
 #include <cstdlib>
-#include <type_traits>
 #include <vector>
 
 #include "../../include/hpccg_hip_poly_group.h"
 #include "hpccg_group.h"
-#include "hpccg_jacobi.h"
-#include "hpccg_poly_bodies.h"
-#include "hpccg_poly_coeffs.h"
-#include "hpccg_spmm.h"
+#include "hpccg_poly_host.h"
 
 #pragma clang fp contract(off)
 
@@ -155,42 +151,15 @@ __global__ __launch_bounds__(kBlock) void k_poly_group_bound_top(const double* _
 // ---------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------
-// One member's workspace: the columns with dd and the two z buffers, the cached
-// 1 / a_ii with its verdict and the member's part of Jacobi's bound, a slot for
-// a caller's m, the bound's vectors. The call's degree and scalars are kept on
-// every member; the spectrum and the traces of the last solve with member 0.
-struct Workspace : TraceWorkspace, GroupMember, JacobiCache {
-    double *r = nullptr, *x = nullptr, *b = nullptr;
-    double *dd = nullptr, *zbuf = nullptr;  // zbuf: two sets of cap columns in the guarded p layout
-    // the bound's vectors (kept while the columns grow, counted in rest_bytes);
-    // qbuf: one guarded column
-    double *qbuf = nullptr, *smax = nullptr, *lmax_dev = nullptr;
-    bool jac_lmax_built = false;
-    double jac_lmax = 0.0;  // this member's rows' part of the bound with m = 1 / a_ii
-    // the call being run
-    int degree = 0;
-    double cheb0 = 0.0, aj[kPolyMaxDegree + 1] = {}, bj[kPolyMaxDegree + 1] = {};
-    bool solved = false;  // (member 0)
-    double last_lmin = 0.0, last_lmax = 0.0;
-
-    Workspace() { ndots = 3; }
-
-    void free_own_vectors()
-    {
-        for (double* q : {r, x, b, dd, zbuf})
-            if (q) (void)hipFree(q);
-        r = x = b = dd = zbuf = nullptr;
-    }
-    void free_bound_vectors()
-    {
-        for (double* q : {qbuf, smax, lmax_dev})
-            if (q) (void)hipFree(q);
-        qbuf = smax = lmax_dev = nullptr;
-    }
+// One member's workspace (hpccg_poly_host.h's, with the member's events and
+// p0): the columns with dd and the two z buffers, the cached 1 / a_ii with its
+// verdict and the member's part of Jacobi's bound, a slot for a caller's m, the
+// bound's vectors. The call's degree and scalars are kept on every member; the
+// spectrum and the traces of the last solve with member 0.
+struct Workspace : PolyWorkspace, GroupMember {
     void free_own_rest()
     {
-        free_bound_vectors();
-        free_cache();
+        PolyWorkspace::free_own_rest();
         destroy_events();
     }
 };
@@ -200,29 +169,39 @@ constexpr const char* kGroupWho = "group poly";
 // a group of one is checked and run like any other: nothing forwards it
 constexpr bool kOneForwarded = false;
 
-// The member's cache (hpccg_jacobi.h), its two events and the bound's vectors
-// (zeroed: q's guard zones and padding are read and never stored; its ghost
-// planes by the halo only).
+// What hpccg_poly_host.h's launchers run: this unit's kernels, on a member's rows.
+struct GroupPoly {
+    using Args = PolyArgs;
+    using Workspace = hpccg::Workspace;
+    static long long row0(const Workspace* w) { return w->p0; }
+
+    static constexpr auto init = k_poly_group_init;
+    template <int kR, bool kPre>
+    static constexpr auto p = k_poly_group_p<kR, kPre>;
+    template <int kW, int kR, int kWaves>
+    static constexpr auto spmm_a = k_poly_group_spmm_a<kW, kR, kWaves>;
+    template <int kR>
+    static constexpr auto spmm_sell = k_poly_group_spmm_sell<kR>;
+    template <int kR, bool kCheb>
+    static constexpr auto update = k_poly_group_update<kR, kCheb>;
+    template <int kW, int kR, int kWaves>
+    static constexpr auto step = k_poly_group_step<kW, kR, kWaves>;
+    template <int kR>
+    static constexpr auto step_sell = k_poly_group_step_sell<kR>;
+    static constexpr auto finalize = k_poly_group_finalize;
+};
+
+// The member's cache (hpccg_jacobi.h), its two events and the bound's vectors.
 int ensure_rest(Workspace* w)
 {
     HIP_TRY(hipSetDevice(w->v.device));
     TRY(w->create_events());
     TRY(ensure_cache(w));
     w->p0 = guarded_p_column(w->v).p0;
-    if (w->qbuf) return 0;
-    const long long before = w->bytes;  // (alloc_zero counts into bytes: the columns')
-    int rc = alloc_zero(w, &w->qbuf, (size_t)guarded_p_column(w->v).pcs);
-    if (!rc) rc = alloc_zero(w, &w->smax, (size_t)std::max(w->v.nslices, 1));
-    if (!rc) rc = alloc_zero(w, &w->lmax_dev, 1);
-    if (rc)
-        w->free_bound_vectors();
-    else
-        w->rest_bytes += w->bytes - before;
-    w->bytes = before;
-    return rc;
+    return ensure_bound_vectors(w, guarded_p_column(w->v).pcs);
 }
 
-int ensure_jacobi(Workspace* w, int r)
+int ensure_member_jacobi(Workspace* w, int r)
 {
     int row = -1;
     TRY(build_jacobi(w, k_poly_group_diag, &row));
@@ -234,7 +213,7 @@ int ensure_jacobi(Workspace* w, int r)
     return 0;
 }
 
-int stage_minv(Workspace* w, int r, const double* minv)
+int stage_member_minv(Workspace* w, int r, const double* minv)
 {
     int row = -1;
     TRY(load_minv(w, minv, hipMemcpyDeviceToDevice, k_poly_group_check, &row));
@@ -260,9 +239,9 @@ int group_preconditioner(hpccg_hip_matrix* const* Ms, PolyGroup* G, const double
         TRY(g_ws<Workspace>.record(Ms[r], G->v[r], &G->w[r]));
         TRY(ensure_rest(G->w[r]));
         if (minv)
-            TRY(stage_minv(G->w[r], r, minv[r]));
+            TRY(stage_member_minv(G->w[r], r, minv[r]));
         else
-            TRY(ensure_jacobi(G->w[r], r));
+            TRY(ensure_member_jacobi(G->w[r], r));
         (*m)[r] = minv ? G->w[r]->muser : G->w[r]->jac;
     }
     return 0;
@@ -340,157 +319,6 @@ int jacobi_group_bound(const PolyGroup& G, const std::vector<const double*>& m, 
     return 0;
 }
 
-// Room for ncols columns and a history of max_iter + 1 entries per column.
-int ensure_vectors(Workspace* w, int ncols, int max_iter)
-{
-    const size_t npad = (size_t)w->v.npad;
-    const PColumn pc = guarded_p_column(w->v);
-    return ensure_columns(w, ncols, max_iter, true, pc.pcs, 3, [&](int cap) {
-        TRY(alloc_zero(w, &w->r, npad * cap));
-        TRY(alloc_zero(w, &w->x, npad * cap));
-        TRY(alloc_zero(w, &w->b, npad * cap));
-        TRY(alloc_zero(w, &w->dd, npad * cap));
-        // zeroed: z's guard zones and padding are read and never stored; its
-        // ghost planes by the halo only
-        TRY(alloc_zero(w, &w->zbuf, 2 * (size_t)pc.pcs * cap));
-        return 0;
-    });
-}
-
-// z buffer `which` (0, 1): local row 0 of column 0
-double* z_of(const Workspace* w, int which)
-{
-    return w->zbuf + (size_t)which * (size_t)w->pcs * (size_t)w->cap + w->p0;
-}
-
-PolyArgs make_args(const Workspace* w, int nrhs, const double* m)
-{
-    const MatrixView& v = w->v;
-    PolyArgs a{};
-    fill_args(&a, w, nrhs);
-    a.tri = 1;
-    a.p = w->pbuf + w->p0;
-    a.r = w->r;
-    a.rcs = w->vcs;
-    a.x = w->x;
-    a.b = w->b;
-    a.minv = m;
-    a.aval = v.aval;
-    a.vals = v.vals;
-    a.dd = w->dd;
-    a.cheb0 = w->cheb0;
-    return a;
-}
-
-// f(std::integral_constant<int, kR>) for the chunk's column count R = 1, 2, 4.
-template <class F>
-void with_columns(int R, F f)
-{
-    if (R == 4)
-        f(std::integral_constant<int, 4>{});
-    else if (R == 2)
-        f(std::integral_constant<int, 2>{});
-    else
-        f(std::integral_constant<int, 1>{});
-}
-
-// The SpMM forms of a chunk (the pcg library's plan choices): f(width, kR, kWaves).
-template <class F>
-void with_spmm_form(const PolyArgs& a, int R, F f)
-{
-    using std::integral_constant;
-    if (a.a_width == 27 && R == 4 && a.nt)
-        f(integral_constant<int, 27>{}, integral_constant<int, 4>{}, integral_constant<int, 5>{});
-    else if (a.a_width == 27)
-        with_columns(R, [&](auto r) { f(integral_constant<int, 27>{}, r, integral_constant<int, 4>{}); });
-    else if (a.a_width == 7)
-        with_columns(R, [&](auto r) { f(integral_constant<int, 7>{}, r, integral_constant<int, 4>{}); });
-    else
-        with_columns(R, [&](auto r) { f(integral_constant<int, 0>{}, r, integral_constant<int, 4>{}); });
-}
-
-void launch_spmm(const Workspace* w, PolyArgs a, bool prologue)
-{
-    const dim3 g(a.grid), b(kBlock);
-    hipStream_t s = w->v.stream;
-    for_chunks(a.nrhs, true, [&](int c0, int R) {
-        a.c0 = c0;
-        if (!w->v.has_a)
-            with_columns(R, [&](auto r) {
-                hipLaunchKernelGGL((k_poly_group_spmm_sell<decltype(r)::value>), g, b, 0, s, a, prologue);
-            });
-        else
-            with_spmm_form(a, R, [&](auto wd, auto r, auto wv) {
-                hipLaunchKernelGGL(
-                    (k_poly_group_spmm_a<decltype(wd)::value, decltype(r)::value, decltype(wv)::value>), g, b, 0, s, a,
-                    prologue);
-            });
-    });
-}
-
-// d == 0: z = m r in the register; else the last step's z (buffer d & 1, the
-// member's own rows only) in r's place.
-void launch_p(const Workspace* w, PolyArgs a, bool prologue)
-{
-    const dim3 g(a.grid), b(kBlock);
-    hipStream_t s = w->v.stream;
-    const int d = w->degree;
-    if (d > 0) {
-        a.r = z_of(w, d & 1);
-        a.rcs = a.pcs;
-    }
-    for_chunks(a.nrhs, true, [&](int c0, int R) {
-        a.c0 = c0;
-        with_columns(R, [&](auto r) {
-            if (d > 0)
-                hipLaunchKernelGGL((k_poly_group_p<decltype(r)::value, false>), g, b, 0, s, a, prologue);
-            else
-                hipLaunchKernelGGL((k_poly_group_p<decltype(r)::value, true>), g, b, 0, s, a, prologue);
-        });
-    });
-}
-
-// The update of one member, with step 0 into z buffer 0 where d >= 1.
-void launch_update(const Workspace* w, PolyArgs a, bool prologue)
-{
-    const dim3 g(a.grid), b(kBlock);
-    hipStream_t s = w->v.stream;
-    const int d = w->degree;
-    a.zout = z_of(w, 0);
-    for_chunks(a.nrhs, true, [&](int c0, int R) {
-        a.c0 = c0;
-        with_columns(R, [&](auto r) {
-            if (d > 0)
-                hipLaunchKernelGGL((k_poly_group_update<decltype(r)::value, true>), g, b, 0, s, a, prologue);
-            else
-                hipLaunchKernelGGL((k_poly_group_update<decltype(r)::value, false>), g, b, 0, s, a, prologue);
-        });
-    });
-}
-
-// Step j of one member: the SpMM's forms.
-void launch_step(const Workspace* w, PolyArgs a, int j)
-{
-    const dim3 g(a.grid), b(kBlock);
-    hipStream_t s = w->v.stream;
-    a.zin = z_of(w, (j - 1) & 1);
-    a.zout = z_of(w, j & 1);
-    a.aj = w->aj[j];
-    a.bj = w->bj[j];
-    a.last = j == w->degree;
-    for_chunks(a.nrhs, true, [&](int c0, int R) {
-        a.c0 = c0;
-        if (!w->v.has_a)
-            with_columns(
-                R, [&](auto r) { hipLaunchKernelGGL((k_poly_group_step_sell<decltype(r)::value>), g, b, 0, s, a); });
-        else
-            with_spmm_form(a, R, [&](auto wd, auto r, auto wv) {
-                hipLaunchKernelGGL((k_poly_group_step<decltype(wd)::value, decltype(r)::value, decltype(wv)::value>),
-                                   g, b, 0, s, a);
-            });
-    });
-}
-
 // ---------------------------------------------------------------------------
 // The group's update phase (hpccg_group.h's hook): every member's update with
 // step 0, then for j = 1 .. d the halo of z buffer (j - 1) & 1 and every
@@ -524,45 +352,23 @@ int group_poly_update(const PolyGroup& G, int nrhs, bool prologue, HaloLaunch ha
 {
     for (int r = 0; r < G.P; r++) {
         TRY(use(G, r));
-        launch_update(G.w[r], G.a[r], prologue);
+        launch_update0<GroupPoly>(G.w[r], G.a[r], prologue);
     }
     const int d = G.w[0]->degree;
     for (int j = 1; j <= d; j++) {
         const int in = (j - 1) & 1;
-        TRY(group_halo_of(G, nrhs, halo, [&](int r) { return HaloBuf{z_of(G.w[r], in), G.a[r].pcs}; }));
+        TRY(group_halo_of(G, nrhs, halo, [&](int r) { return HaloBuf{z_of<GroupPoly>(G.w[r], in), G.a[r].pcs}; }));
         for (int r = 0; r < G.P; r++) {
             TRY(use(G, r));
-            launch_step(G.w[r], G.a[r], j);
+            launch_step64<GroupPoly>(G.w[r], step_args<GroupPoly>(G.w[r], G.a[r], j));
         }
     }
     return 0;
 }
 
-// (store_total: always 1 here, a member's part; the state is the group sum's)
-void launch_finalize(const Workspace* w, const PolyArgs& a, int which, int store_total)
-{
-    hipLaunchKernelGGL(k_poly_group_finalize, dim3(a.nrhs), dim3(kFinThreads), 0, w->v.stream, a, which, store_total);
-}
-
-void launch_init(const Workspace* w, const PolyArgs& a, int max_iter, double tol)
-{
-    hipLaunchKernelGGL(k_poly_group_init, dim3((a.nrhs + 63) / 64), dim3(64), 0, w->v.stream, a, max_iter, tol);
-}
-
 void launch_group_sum(const Workspace* w, const PolyArgs& a, const GroupTotals& gt, int which)
 {
     hipLaunchKernelGGL(k_poly_group_sum, dim3((a.nrhs + 63) / 64), dim3(64), 0, w->v.stream, a, gt, which);
-}
-
-// A caller's bounds: each finite and >= 0 (0.0: the default); both given, lmin < lmax.
-int check_bounds(double lmin, double lmax)
-{
-    if (!(std::isfinite(lmin) && std::isfinite(lmax) && lmin >= 0.0 && lmax >= 0.0))
-        return fail(HPCCG_HIP_EINVAL,
-                    "group poly: spectrum bounds lmin %g, lmax %g (finite and >= 0 needed; 0: the default)", lmin, lmax);
-    if (lmax > 0.0 && lmin >= lmax)
-        return fail(HPCCG_HIP_EINVAL, "group poly: spectrum bounds lmin %g >= lmax %g", lmin, lmax);
-    return 0;
 }
 
 // copies: the halos by copies (the fallback and the baseline), else by k_poly_group_halo.
@@ -579,32 +385,30 @@ int group_solve(hpccg_hip_matrix* const* Ms, const PolyGroup& G0, int nrhs, cons
     std::vector<const double*> m;
     TRY(group_preconditioner(Ms, &G, minv, &m));
     double cheb0 = 0.0, aj[kPolyMaxDegree + 1] = {}, bj[kPolyMaxDegree + 1] = {};
-    if (degree > 0) {  // (degree 0 applies no polynomial and needs no interval)
-        if (lmax == 0.0)
-            TRY(minv ? compute_group_bound(G, m, copies, nullptr, &lmax) : jacobi_group_bound(G, m, copies, &lmax));
-        if (lmin == 0.0) lmin = lmax / kPolyEigRatio;
-        if (!(lmin > 0.0 && lmin < lmax))
-            return fail(HPCCG_HIP_EINVAL, "group poly: spectrum bounds lmin %g >= lmax %g", lmin, lmax);
-        poly_coefficients(lmin, lmax, degree, &cheb0, aj, bj);
-    } else if (lmin == 0.0 && lmax > 0.0) {
-        lmin = lmax / kPolyEigRatio;
-    }
+    TRY(resolve_interval(kGroupWho, degree, &lmin, &lmax, &cheb0, aj, bj, [&](double* top) {
+        return minv ? compute_group_bound(G, m, copies, nullptr, top) : jacobi_group_bound(G, m, copies, top);
+    }));
     for (int r = 0; r < G.P; r++) {
         Workspace* w = G.w[r];
-        TRY(ensure_vectors(w, nrhs, max_iter));
+        TRY(ensure_vectors(w, nrhs, max_iter, guarded_p_column(w->v).pcs, 3));
         w->degree = degree;
         w->cheb0 = cheb0;
         std::copy(aj, aj + kPolyMaxDegree + 1, w->aj);
         std::copy(bj, bj + kPolyMaxDegree + 1, w->bj);
-        G.a[r] = make_args(w, nrhs, m[r]);
+        G.a[r] = make_args<GroupPoly>(w, nrhs, m[r]);
     }
     G.w[0]->last_lmin = lmin;
     G.w[0]->last_lmax = lmax;
     G.w[0]->solved = true;
     TRY(group_stage_in(G, nrhs, B, ldb, X, ldx));
-    const GroupLaunch<Workspace, PolyArgs> launch = {launch_init,     launch_p,         launch_spmm,
-                                                     launch_update,   launch_finalize,  launch_group_sum,
-                                                     copies ? nullptr : launch_halo, group_poly_update};
+    const GroupLaunch<Workspace, PolyArgs> launch = {launch_init<GroupPoly>,
+                                                     launch_p<GroupPoly>,
+                                                     launch_spmm64<GroupPoly>,
+                                                     launch_update0<GroupPoly>,
+                                                     launch_finalize<GroupPoly>,
+                                                     launch_group_sum,
+                                                     copies ? nullptr : launch_halo,
+                                                     group_poly_update};
     double wall = 0.0;
     TRY(group_run_cg(G, nrhs, max_iter, tol, launch, niters, normr, &wall));
     TRY(group_stage_out(G, nrhs, X, ldx));
@@ -645,7 +449,7 @@ int hpccg_hip_group_poly_solve_device(hpccg_hip_matrix* const* Ms, int nranks, i
     }
     if (degree < 0 || degree > kPolyMaxDegree)
         return fail(HPCCG_HIP_EINVAL, "group poly: degree %d (0 to %d)", degree, kPolyMaxDegree);
-    TRY(check_bounds(lmin, lmax));
+    TRY(check_bounds(kGroupWho, lmin, lmax));
     PolyGroup G;
     TRY(check_group(kGroupWho, Ms, nranks, kOneForwarded, &G));
     TRY(check_group_lds(kGroupWho, G, ldb, ldx, "ldb, ldx"));

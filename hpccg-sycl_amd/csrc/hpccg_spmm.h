@@ -1,8 +1,10 @@
 // hpccg_spmm.h -- the fp64 SpMM loops shared by the units that stream the
 // matrix's own fp64 image for several columns (hpccg_batch.hip,
-// hpccg_pcg.hip, hpccg_pcg_group.hip, hpccg_poly.hip): the slot loop and the
-// x-triple plan over SELL-512-A, the int32-column loop over SELL-512, and the
-// two kernel bodies around them. A
+// hpccg_pcg.hip, hpccg_pcg_group.hip, hpccg_poly.hip, hpccg_poly_group.hip,
+// and hpccg_poly32.hip for the outer SpMM of an inexact image): the slot loop
+// and the x-triple plan over SELL-512-A, the int32-column loop over SELL-512,
+// and the two kernel bodies around them. hpccg_spmm32.h builds the same loops
+// over an fp32 image on the ends policy defined here. A
 // unit's __global__ entry points are thin wrappers over the bodies (their
 // launch bounds and occupancy are the wrapper's); the bodies are templates on
 // the unit's argument struct A, a ColArgs with

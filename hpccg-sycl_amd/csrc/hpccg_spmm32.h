@@ -1,11 +1,19 @@
-// hpccg_spmm32.h -- the fp64 SpMM loops over an fp32 image of the matrix
-// values, for the units that stream such an image for several columns
-// (hpccg_poly32.hip). The image's layout and the loops are the mixed library's
-// (hpccg_mixed.hip, which keeps its own copy: its kernels are not built from
-// this header): slice by slice with the slot-row bases of the image the matrix
-// holds, so the offset tables / int32 columns are shared; inside a slice the
-// slots are interleaved in pairs, slot pair (2q, 2q + 1) laid out so that
-// thread t (rows 2t, 2t + 1) reads one float4
+// hpccg_spmm32.h -- the fp32 image of the matrix values and the fp64 SpMM loops
+// over it, for the units that stream such an image for several columns
+// (hpccg_mixed.hip, hpccg_poly32.hip).
+//   device  the body of a unit's convert kernel; the slot loops over the image
+//           (spmm32_a_slots, slot32_sell) and the two SpMM kernel bodies around
+//           them (spmm32_a_body with the x-triple plan, spmm32_sell_body). A
+//           unit's __global__ entry points are thin wrappers over the bodies;
+//           the mixed unit keeps the frames of its two SpMM kernels (it has no
+//           x-triple arm) and runs the slot loops from here.
+//   host    Image32, the image's record in a unit's workspace, and
+//           ensure_image32, its one builder.
+// The image follows the image the matrix holds (SELL-512-A where it exists,
+// else SELL-512), slice by slice with the same slot-row bases, so the offset
+// tables / int32 columns are shared; inside a slice the slots are interleaved
+// in pairs, slot pair (2q, 2q + 1) laid out so that thread t (rows 2t, 2t + 1)
+// reads one float4
 //   { v[2q][2t], v[2q][2t + 1], v[2q + 1][2t], v[2q + 1][2t + 1] }
 // at (base + 2q) * 512 + 4t; an odd width's last slot is a plain [512 rows]
 // run read 8 B per lane. Exactly 4 B per slot. A value is widened in the
@@ -280,6 +288,79 @@ __device__ __forceinline__ void spmm32_sell_body(const A& a, bool prologue)
     }
     const int row = s * kSliceRows + threadIdx.x * kRpt;
     E::template out<kR>(a, prologue, s, row, act, sum);
+}
+
+// ---------------------------------------------------------------------------
+// host
+// ---------------------------------------------------------------------------
+// The fp32 image of one matrix (a unit's Workspace derives from it): kept while
+// the columns grow, counted in img_bytes; the verdict stays when the image goes.
+struct Image32 {
+    float* img = nullptr;
+    long long img_bytes = 0;
+    bool built = false;
+    long long inexact = 0, out_of_range = 0;
+
+    void free_image()
+    {
+        if (img) (void)hipFree(img);
+        img = nullptr;
+        img_bytes = 0;
+    }
+};
+
+typedef void (*Convert32Kernel)(const double*, const unsigned int*, int, float*, unsigned long long*);
+
+// The fp32 image, built once per matrix on the device from the image it holds,
+// by the unit's convert kernel. who: the name in front of the unit's messages.
+int ensure_image32(Image32* im, const MatrixView& v, Convert32Kernel k_convert, const char* who)
+{
+    auto out_of_range = [&] {
+        return fail(HPCCG_HIP_EINVAL,
+                    "%s: the matrix is outside fp32 range (%lld stored values with no finite, normal fp32 image)", who,
+                    im->out_of_range);
+    };
+    if (im->built) return im->out_of_range ? out_of_range() : 0;
+    hipStream_t s = v.stream;
+    HIP_TRY(hipSetDevice(v.device));
+    const double* vals = v.has_a ? v.aval : v.vals;
+    const unsigned int* tab = v.has_a ? v.abase : v.slice_base;
+    const int width = v.has_a ? v.a_width : 0;
+    long long slot_rows = (long long)v.nslices * width;
+    if (width <= 0) {
+        unsigned int last = 0;
+        HIP_TRY(hipMemcpyAsync(&last, tab + v.nslices, sizeof last, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        slot_rows = last;
+    }
+    const size_t bytes = sizeof(float) * (size_t)std::max<long long>(slot_rows, 1) * kSliceRows;
+    unsigned long long* flags = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&im->img), bytes));
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&flags), 2 * sizeof *flags);
+    unsigned long long h[2] = {0, 0};
+    if (e == hipSuccess) e = hipMemsetAsync(flags, 0, 2 * sizeof *flags, s);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_convert, dim3(v.nslices), dim3(kBlock), 0, s, vals, tab, width, im->img, flags);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h, flags, sizeof h, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (flags) (void)hipFree(flags);
+    if (e != hipSuccess) {
+        (void)hipFree(im->img);
+        im->img = nullptr;
+        return fail(e == hipErrorOutOfMemory ? HPCCG_HIP_ENOMEM : HPCCG_HIP_EHIP, "%s: building the fp32 image: %s",
+                    who, hipGetErrorString(e));
+    }
+    im->built = true;
+    im->inexact = (long long)h[0];
+    im->out_of_range = (long long)h[1];
+    im->img_bytes = (long long)bytes;
+    if (im->out_of_range) {  // never solved with: the image goes, the verdict stays
+        im->free_image();
+        return out_of_range();
+    }
+    return 0;
 }
 
 }  // namespace

@@ -302,6 +302,7 @@ struct hpccg_hip_matrix {
     int fuse_p = -1;      // -1 auto: on where the kernel forms p_k itself
     int fuse_update = -1; // the update as trailing blocks of the SpMV launch; -1 auto (fuse_update_effective)
     int resident_update = -1;     // the resident pair kernels (k_spmv_ar, k_cg_persist; resident_of, persist_ok)
+    int nt_opt = -1;              // option nt (diagnostics): -1 auto (image_big), 0 / 1 force the matrix loads' hint
     int resident_retries = 0;     // solves re-run after a resident launch's wait expired (resident_retry)
     int resident_failed = 0;      // a resident launch's wait expired (GPU shared): the unit + update launch from then on
     int resident_used = 0;        // the last solve ran k_spmv_ar
@@ -1099,8 +1100,11 @@ bool image_big(const hpccg_hip_matrix* M)
 }
 
 // The matrix streams' cache policy: non-temporal loads beyond the Infinity
-// Cache (a forced policy measured even or slower: DESIGN.md 4, what was dropped)
-bool nt_load_of(const hpccg_hip_matrix* M) { return image_big(M); }
+// Cache (a forced policy measured even or slower: DESIGN.md 4, what was dropped).
+// Option nt (diagnostics) forces the flag, so the tests run the non-temporal
+// kernel forms at small shapes; the kernel choice and the vector stores
+// (choose_kernel, nt_store_effective) keep following the image's size.
+bool nt_load_of(const hpccg_hip_matrix* M) { return M->nt_opt >= 0 ? M->nt_opt != 0 : image_big(M); }
 
 bool kernel_available(const hpccg_hip_matrix* M, int k)
 {
@@ -1439,6 +1443,8 @@ bool persist_multi_of(const hpccg_hip_matrix* M)
 }
 bool persist_ok(const hpccg_hip_matrix* M)
 {
+    // (k_cg_persist<true> has no production path -- DESIGN.md 4 -- and the forced flag opens none)
+    if (M->nt_opt == 1) return false;
     if (!(persist_shape(M) && resident_of(M)) && !persist_multi_of(M)) return false;
     // (byte offsets of the p ring in 32 bits)
     if (M->pstride * 2 * (long long)sizeof(double) >= (1LL << 31)) return false;
@@ -3914,7 +3920,7 @@ int hpccg_hip_matrix_vectors(hpccg_hip_matrix* M, double** b, double** x0, doubl
 // Options (hpccg_hip.h documents each): twelve settings of the solve --
 // use_graph, spmv_kernel, fuse_p, fold, x_defer, x_ring, fuse_update,
 // resident_update, graph_chunk, a2_ring, peer_allreduce, halo_pull -- and
-// diagnostics (event_timing, force_comm, spin_budget_us, dbg_*). Variants
+// diagnostics (event_timing, force_comm, spin_budget_us, nt, dbg_*). Variants
 // that measured even or slower than the defaults were removed (DESIGN.md 4,
 // "What was dropped"); git history keeps them.
 int hpccg_hip_set_option(hpccg_hip_matrix* M, const char* key, long long value)
@@ -3953,6 +3959,10 @@ int hpccg_hip_set_option(hpccg_hip_matrix* M, const char* key, long long value)
                                              "or 1 (the per-iteration resident launch only)");
         M->resident_update = (int)value;
         if (value) M->resident_failed = 0;
+    } else if (!std::strcmp(key, "nt")) {
+        if (value < -1 || value > 1)
+            return set_err(HPCCG_HIP_EINVAL, "nt must be -1 (auto: images beyond the Infinity Cache), 0 or 1");
+        M->nt_opt = (int)value;  // (the graph cache compares the kernel arguments: a changed a.nt re-captures)
     } else if (!std::strcmp(key, "graph_chunk")) {
         if (value < 1 || value > 4096) return set_err(HPCCG_HIP_EINVAL, "graph_chunk must be 1..4096");
         M->graph_iters = (int)value;

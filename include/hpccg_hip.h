@@ -242,7 +242,14 @@ int hpccg_hip_last_trace(const hpccg_hip_matrix* M, double* out, int cap);
  *                   published, so the solve must time out (0 = off)
  *   "dbg_resident_stall" (retry test) 1 = the resident launches' p.Ap wait
  *                   never sees the total, so it expires
- * get only: "has_sell", "has_a", "has_pairs", "a_width", "lds_doubles", "nt",
+ *   "nt"            the matrix loads' non-temporal hint in every library's SpMV
+ *                   and SpMM kernels: -1 auto (default: on for images beyond
+ *                   the 256 MB Infinity Cache), 0 / 1 force it, so the tests
+ *                   run both kernel forms at small shapes; get: the value in
+ *                   effect. The kernel choice and "nt_store" keep following
+ *                   the image's size, and while it is forced to 1 the
+ *                   persistent launch is not taken (k_spmv_ar still is)
+ * get only: "has_sell", "has_a", "has_pairs", "a_width", "lds_doubles",
  * "nt_store", "halo_mode", "num_external", "group_fold" (the last in-process
  * group solve summed its dots in its members' kernels), "resident_retries",
  * "peer_auto_ok", "pull_auto_ok", "proto_auto_ok", "persist_auto_ok" (the

@@ -435,6 +435,56 @@ def poly32_lib() -> C.CDLL:
     return L
 
 
+POLY32_GROUP_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_poly32_group.so")
+_poly32_group_lib = None
+
+
+def poly32_group_lib() -> C.CDLL:
+    """Load libhpccg_hip_poly32_group.so (include/hpccg_hip_poly32_group.h) on
+    first use. It is linked against libhpccg_hip.so beside it, so lib() is
+    loaded first and both share one copy of the main library."""
+    global _poly32_group_lib
+    if _poly32_group_lib is not None:
+        return _poly32_group_lib
+    if os.environ.get("HPCCG_HIP_LIB", LIB_PATH) != LIB_PATH:
+        raise HPCCGError("the group poly32 library runs on the in-tree libhpccg_hip.so only (HPCCG_HIP_LIB is set)")
+    lib()
+    if not os.path.exists(POLY32_GROUP_LIB_PATH):
+        raise HPCCGError(f"{POLY32_GROUP_LIB_PATH} missing: run build() (the group fp32-image polynomial solve has "
+                         "no fallback)")
+    try:
+        L = C.CDLL(POLY32_GROUP_LIB_PATH)
+    except OSError as e:
+        raise HPCCGError(f"{POLY32_GROUP_LIB_PATH} does not load: {e}") from e
+    vp, ip, dp, lp = C.c_void_p, C.c_int, C.c_double, C.c_longlong
+    PI, PD, PV, PL = C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(vp), C.POINTER(lp)
+    sig = {
+        "hpccg_hip_group_poly32_abi_version": (ip, []),
+        "hpccg_hip_group_poly32_solve_device": (ip, [PV, ip, ip, PV, PL, PV, PL, PV, ip, dp, dp, ip, dp, PI, PD, PD]),
+        "hpccg_hip_group_poly32_bound": (ip, [PV, ip, PV, PD]),
+        "hpccg_hip_group_poly32_last_spectrum": (ip, [PV, ip, PD, PD]),
+        "hpccg_hip_group_poly32_last_trace": (ip, [PV, ip, ip, PD, ip]),
+        "hpccg_hip_group_poly32_info": (ip, [PV, ip, PL]),
+        "hpccg_hip_group_poly32_release": (ip, [vp]),
+        "hpccg_hip_group_poly32_workspace_bytes": (ip, [vp, PL]),
+        "hpccg_hip_group_poly32_live_workspaces": (ip, [PI]),
+    }
+    for name, (res, args) in sig.items():
+        f = getattr(L, name)
+        f.restype = res
+        f.argtypes = args
+    _poly32_group_lib = L
+    return L
+
+
+def group_poly32_exported_symbols() -> list[str]:
+    """Functions include/hpccg_hip_poly32_group.h declares (checked by the CPU suite)."""
+    import re
+    with open(os.path.join(ROOT, "include", "hpccg_hip_poly32_group.h")) as f:
+        text = f.read()
+    return sorted(set(re.findall(r"\b(hpccg_hip_group_poly32_\w+)\s*\(", text)))
+
+
 def poly32_exported_symbols() -> list[str]:
     """Functions include/hpccg_hip_poly32.h declares (checked by the CPU suite)."""
     import re
@@ -1497,18 +1547,19 @@ def _group_minvs(Ms, minvs):
 class _halo_copies_env:
     """The library's halo-by-copies switch set (or cleared) for one call."""
 
-    def __init__(self, on):
+    def __init__(self, on, name=_POLY_HALO_COPIES_ENV):
         self.on = on
+        self.name = name
 
     def __enter__(self):
-        self.saved = os.environ.pop(_POLY_HALO_COPIES_ENV, None)
+        self.saved = os.environ.pop(self.name, None)
         if self.on:
-            os.environ[_POLY_HALO_COPIES_ENV] = "1"
+            os.environ[self.name] = "1"
 
     def __exit__(self, *exc):
-        os.environ.pop(_POLY_HALO_COPIES_ENV, None)
+        os.environ.pop(self.name, None)
         if self.saved is not None:
-            os.environ[_POLY_HALO_COPIES_ENV] = self.saved
+            os.environ[self.name] = self.saved
 
 
 def group_HPCCG_poly(Ms: list, Bs, Xs, degree: int = 2, lmin=None, lmax=None, minvs=None, max_iter: int = 500,
@@ -1601,6 +1652,114 @@ def group_poly_live_workspaces() -> int:
         return 0
     c = C.c_int(0)
     _check(_poly_group_lib.hpccg_hip_group_poly_live_workspaces(C.byref(c)), "group_poly_live_workspaces")
+    return c.value
+
+
+# ---------------------------------------------------------------------------
+# ... with the steps streamed from the members' fp32 images (include/hpccg_hip_poly32_group.h)
+# ---------------------------------------------------------------------------
+_POLY32_HALO_COPIES_ENV = "HPCCG_GROUP_POLY32_HALO_COPIES"
+
+
+def group_HPCCG_poly32(Ms: list, Bs, Xs, degree: int = 2, lmin=None, lmax=None, minvs=None, max_iter: int = 500,
+                       tolerance: float = 0.0, nrhs=None, ldb=None, ldx=None, halo_copies: bool = False):
+    """group_HPCCG_poly with every member's polynomial steps streamed from an
+    fp32 image of its rows (hpccg_hip_group_poly32_solve_device); the system
+    solved is the fp64 one. Where every member's image is exact
+    (group_poly32_info) every column is group_HPCCG_poly bit for bit; degree 0 is
+    group_HPCCG_pcg bit for bit on any matrix; a group of one is HPCCG_poly32 bit
+    for bit. The arguments and the result are group_HPCCG_poly's."""
+    L = poly32_group_lib()
+    P = len(Ms)
+    if len(Bs) != P or len(Xs) != P:
+        raise HPCCGError(f"{P} members, {len(Bs)} B and {len(Xs)} X column sets")
+    hs = (C.c_void_p * P)(*[M.h for M in Ms])
+    bp, nb, ldb_ = _group_cols(Bs, nrhs, ldb, "Bs")
+    xp, nx_, ldx_ = _group_cols(Xs, nrhs, ldx, "Xs")
+    if nb != nx_:
+        raise HPCCGError(f"Bs holds {nb} columns, Xs {nx_}")
+    mp = _group_minvs(Ms, minvs)
+    it = np.zeros(max(nb, 1), np.int32)
+    nr = np.zeros(max(nb, 1), np.float64)
+    times = np.zeros(7, np.float64)
+    with _halo_copies_env(halo_copies, _POLY32_HALO_COPIES_ENV):
+        rc = L.hpccg_hip_group_poly32_solve_device(hs, P, nb, bp, ldb_, xp, ldx_, mp, int(degree),
+                                                   0.0 if lmin is None else float(lmin),
+                                                   0.0 if lmax is None else float(lmax), max_iter, tolerance,
+                                                   it.ctypes.data_as(C.POINTER(C.c_int)),
+                                                   nr.ctypes.data_as(C.POINTER(C.c_double)),
+                                                   times.ctypes.data_as(C.POINTER(C.c_double)))
+    _check(rc, "group_HPCCG_poly32")
+    return it[:nb], nr[:nb], times
+
+
+def group_poly32_bound(Ms: list, minvs=None) -> float:
+    """The symmetric Gershgorin bound of the group's global fp64 matrix that
+    group_HPCCG_poly32 takes for lmax (group_poly_bound's value); minvs: per
+    member a device tensor / pointer of its nrow entries, or None for Jacobi."""
+    P = len(Ms)
+    hs = (C.c_void_p * P)(*[M.h for M in Ms])
+    v = C.c_double(0.0)
+    _check(poly32_group_lib().hpccg_hip_group_poly32_bound(hs, P, _group_minvs(Ms, minvs), C.byref(v)),
+           "group_poly32_bound")
+    return v.value
+
+
+def group_poly32_info(Ms: list) -> list:
+    """The members' fp32 images of the group poly32 library (built on first
+    use), one dict per member: exact (every value of the member's rows survives
+    double -> float -> double), image_bytes, inexact_values."""
+    P = len(Ms)
+    hs = (C.c_void_p * P)(*[M.h for M in Ms])
+    a = (C.c_longlong * (4 * P))()
+    _check(poly32_group_lib().hpccg_hip_group_poly32_info(hs, P, a), "group_poly32_info")
+    return [{"exact": int(a[4 * r]),"image_bytes": int(a[4 * r + 1]), "inexact_values": int(a[4 * r + 2])}
+            for r in range(P)]
+
+
+def group_last_trace_poly32(Ms: list, col: int, cap: int = 100000) -> np.ndarray:
+    """Residual trace (norm of r) of column col of the last group_HPCCG_poly32 on Ms."""
+    P = len(Ms)
+    hs = (C.c_void_p * P)(*[M.h for M in Ms])
+    out = np.zeros(cap, np.float64)
+    n = poly32_group_lib().hpccg_hip_group_poly32_last_trace(hs, P, int(col),
+                                                             out.ctypes.data_as(C.POINTER(C.c_double)), cap)
+    if n < 0:
+        _check(n, "group_last_trace_poly32")
+    return out[:n]
+
+
+def group_last_spectrum_poly32(Ms: list) -> tuple:
+    """(lmin, lmax) the last group_HPCCG_poly32 on Ms used."""
+    P = len(Ms)
+    hs = (C.c_void_p * P)(*[M.h for M in Ms])
+    lo, hi = C.c_double(0.0), C.c_double(0.0)
+    _check(poly32_group_lib().hpccg_hip_group_poly32_last_spectrum(hs, P, C.byref(lo), C.byref(hi)),
+           "group_last_spectrum_poly32")
+    return lo.value, hi.value
+
+
+def group_poly32_workspace_bytes(M: Matrix) -> int:
+    """Device bytes member M's group poly32 workspace holds, its fp32 image included (0: none)."""
+    if _poly32_group_lib is None:
+        return 0
+    v = C.c_longlong(0)
+    _check(_poly32_group_lib.hpccg_hip_group_poly32_workspace_bytes(M.h, C.byref(v)), "group_poly32_workspace_bytes")
+    return v.value
+
+
+def group_poly32_release(M: Matrix) -> None:
+    """Free member M's group poly32 workspace (with its caches and its fp32 image) now (close() does it too)."""
+    if M.h and _poly32_group_lib is not None:
+        _check(_poly32_group_lib.hpccg_hip_group_poly32_release(M.h), "group_poly32_release")
+
+
+def group_poly32_live_workspaces() -> int:
+    """Matrices that hold a group poly32 workspace (0 when the library was never loaded)."""
+    if _poly32_group_lib is None:
+        return 0
+    c = C.c_int(0)
+    _check(_poly32_group_lib.hpccg_hip_group_poly32_live_workspaces(C.byref(c)), "group_poly32_live_workspaces")
     return c.value
 
 

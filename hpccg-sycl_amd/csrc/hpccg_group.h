@@ -1,6 +1,6 @@
 // hpccg_group.h -- the column recurrence of hpccg_columns.h over an in-process
 // rank group, shared by the group solvers (hpccg_batch.hip, hpccg_pcg_group.hip,
-// hpccg_poly_group.hip).
+// hpccg_poly_group.hip, hpccg_poly32_group.hip).
 // Member r is rank r of a z-slab job: it runs its unit's kernels on its own
 // rows, on its own stream, in a workspace of its own; the ghost planes of every
 // column's p move between the members after the p update, each member's
@@ -251,7 +251,7 @@ struct HaloBuf {
 // (launch_halo null) by copies, one per column and side. Frozen columns' planes
 // move too (their vectors no longer change: harmless). What keeps a neighbour
 // from overwriting its rows before they have been read here is the caller's to
-// argue (group_halo below: p; hpccg_poly_group.hip: the two z buffers).
+// argue (group_halo below: p; hpccg_poly_group_host.h: the two z buffers).
 template <class W, class A, class Buf>
 int group_halo_of(const Group<W, A>& G, int nrhs, HaloLaunch launch_halo, Buf buf)
 {

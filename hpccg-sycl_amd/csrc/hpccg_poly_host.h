@@ -1,6 +1,7 @@
 // hpccg_poly_host.h -- the host code of the Chebyshev polynomial preconditioned
-// CG, shared by the polynomial units (hpccg_poly.hip, hpccg_poly32.hip,
-// hpccg_poly_group.hip): the workspace's polynomial state, the dispatch on a
+// CG, shared by the polynomial units (hpccg_poly.hip, hpccg_poly32.hip and,
+// under hpccg_poly_group_host.h, hpccg_poly_group.hip and
+// hpccg_poly32_group.hip): the workspace's polynomial state, the dispatch on a
 // chunk's columns and fp64 SpMM form, the kernel arguments, the launchers, the
 // checks of a caller's bounds and the interval with its coefficients; for the
 // one-rank units (poly, poly32) also the matrix check, the preconditioner, the

@@ -1,6 +1,6 @@
 // hpccg_spmm32.h -- the fp32 image of the matrix values and the fp64 SpMM loops
 // over it, for the units that stream such an image for several columns
-// (hpccg_mixed.hip, hpccg_poly32.hip).
+// (hpccg_mixed.hip, hpccg_poly32.hip, hpccg_poly32_group.hip).
 //   device  the body of a unit's convert kernel; the slot loops over the image
 //           (spmm32_a_slots, slot32_sell) and the two SpMM kernel bodies around
 //           them (spmm32_a_body with the x-triple plan, spmm32_sell_body). A

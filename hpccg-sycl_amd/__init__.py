@@ -272,6 +272,45 @@ def pcg_lib() -> C.CDLL:
     return L
 
 
+SRCG_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_srcg.so")
+_srcg_lib = None
+
+
+def srcg_lib() -> C.CDLL:
+    """Load libhpccg_hip_srcg.so (include/hpccg_hip_srcg.h) on first use. It is
+    linked against libhpccg_hip.so beside it, so lib() is loaded first and both
+    share one copy of the main library."""
+    global _srcg_lib
+    if _srcg_lib is not None:
+        return _srcg_lib
+    if os.environ.get("HPCCG_HIP_LIB", LIB_PATH) != LIB_PATH:
+        raise HPCCGError("the srcg library runs on the in-tree libhpccg_hip.so only (HPCCG_HIP_LIB is set)")
+    lib()
+    if not os.path.exists(SRCG_LIB_PATH):
+        raise HPCCGError(f"{SRCG_LIB_PATH} missing: run build() (the single-reduction solve has no fallback)")
+    try:
+        L = C.CDLL(SRCG_LIB_PATH)
+    except OSError as e:
+        raise HPCCGError(f"{SRCG_LIB_PATH} does not load: {e}") from e
+    vp, ip, dp, lp = C.c_void_p, C.c_int, C.c_double, C.c_longlong
+    PI, PD = C.POINTER(C.c_int), C.POINTER(C.c_double)
+    sig = {
+        "hpccg_hip_srcg_abi_version": (ip, []),
+        "hpccg_hip_srcg_solve_device": (ip, [vp, ip, vp, lp, vp, lp, vp, ip, dp, PI, PD, PD]),
+        "hpccg_hip_srcg_solve": (ip, [vp, ip, vp, lp, vp, lp, vp, ip, dp, PI, PD, PD]),
+        "hpccg_hip_srcg_last_trace": (ip, [vp, ip, PD, ip]),
+        "hpccg_hip_srcg_release": (ip, [vp]),
+        "hpccg_hip_srcg_workspace_bytes": (ip, [vp, C.POINTER(lp)]),
+        "hpccg_hip_srcg_live_workspaces": (ip, [PI]),
+    }
+    for name, (res, args) in sig.items():
+        f = getattr(L, name)
+        f.restype = res
+        f.argtypes = args
+    _srcg_lib = L
+    return L
+
+
 PCG_GROUP_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_pcg_group.so")
 _pcg_group_lib = None
 
@@ -523,6 +562,14 @@ def pcg_exported_symbols() -> list[str]:
     with open(os.path.join(ROOT, "include", "hpccg_hip_pcg.h")) as f:
         text = f.read()
     return sorted(set(re.findall(r"\b(hpccg_hip_pcg_\w+)\s*\(", text)))
+
+
+def srcg_exported_symbols() -> list[str]:
+    """Functions include/hpccg_hip_srcg.h declares (checked by the CPU suite)."""
+    import re
+    with open(os.path.join(ROOT, "include", "hpccg_hip_srcg.h")) as f:
+        text = f.read()
+    return sorted(set(re.findall(r"\b(hpccg_hip_srcg_\w+)\s*\(", text)))
 
 
 def mixed_exported_symbols() -> list[str]:
@@ -884,6 +931,26 @@ class Matrix:
         _check(_pcg_lib.hpccg_hip_pcg_workspace_bytes(self.h, C.byref(v)), "pcg_workspace_bytes")
         return v.value
 
+    def last_trace_srcg(self, col: int, cap: int = 100000) -> np.ndarray:
+        """Residual trace (norm of r) of column col of the last HPCCG_srcg on this matrix."""
+        out = np.zeros(cap, np.float64)
+        n = srcg_lib().hpccg_hip_srcg_last_trace(self.h, int(col), out.ctypes.data_as(C.POINTER(C.c_double)), cap)
+        if n < 0:
+            _check(n, "last_trace_srcg")
+        return out[:n]
+
+    def srcg_release(self) -> None:
+        """Free this matrix's srcg workspace (with its cached 1 / a_ii) now (close() does it too)."""
+        if self.h and _srcg_lib is not None:
+            _check(_srcg_lib.hpccg_hip_srcg_release(self.h), "srcg_release")
+
+    def srcg_workspace_bytes(self) -> int:
+        if _srcg_lib is None:
+            return 0
+        v = C.c_longlong(0)
+        _check(_srcg_lib.hpccg_hip_srcg_workspace_bytes(self.h, C.byref(v)), "srcg_workspace_bytes")
+        return v.value
+
     def last_trace_poly(self, col: int, cap: int = 100000) -> np.ndarray:
         """Residual trace (norm of r) of column col of the last HPCCG_poly on this matrix."""
         out = np.zeros(cap, np.float64)
@@ -1165,6 +1232,44 @@ def pcg_live_workspaces() -> int:
         return 0
     c = C.c_int(0)
     _check(_pcg_lib.hpccg_hip_pcg_live_workspaces(C.byref(c)), "pcg_live_workspaces")
+    return c.value
+
+
+# ---------------------------------------------------------------------------
+# single-reduction preconditioned solve (include/hpccg_hip_srcg.h)
+# ---------------------------------------------------------------------------
+def HPCCG_srcg(M: Matrix, B, X, max_iter: int = 500, tolerance: float = 0.0, minv=None, device=False, nrhs=None,
+               ldb=None, ldx=None):
+    """HPCCG_pcg in the single-reduction (Chronopoulos-Gear) form
+    (hpccg_hip_srcg_solve[_device]): one finalize and three launches per
+    iteration for one more vector. Its first iteration is HPCCG_pcg's bit for
+    bit; later ones agree to rounding. B, X, minv and the return value: as
+    HPCCG_pcg. X is updated in place."""
+    L = srcg_lib()
+    B, X = _one_column(B, "B"), _one_column(X, "X")
+    bp, nb, ldb_ = _cols(B, nrhs, ldb, "B")
+    xp, nx_, ldx_ = _cols(X, nrhs, ldx, "X")
+    if nb != nx_:
+        raise HPCCGError(f"B holds {nb} columns, X {nx_}")
+    if not device and not (isinstance(B, np.ndarray) and isinstance(X, np.ndarray)):
+        raise HPCCGError("host solve: B and X are numpy arrays")
+    mp, keep = (None, None) if minv is None else _minv_ptr(M, minv, device)
+    it = np.zeros(max(nb, 1), np.int32)
+    nr = np.zeros(max(nb, 1), np.float64)
+    times = np.zeros(7, np.float64)
+    f = L.hpccg_hip_srcg_solve_device if device else L.hpccg_hip_srcg_solve
+    rc = f(M.h, nb, bp, ldb_, xp, ldx_, mp, max_iter, tolerance, it.ctypes.data_as(C.POINTER(C.c_int)),
+           nr.ctypes.data_as(C.POINTER(C.c_double)), times.ctypes.data_as(C.POINTER(C.c_double)))
+    _check(rc, "HPCCG_srcg")
+    return rc, it[:nb], nr[:nb], times
+
+
+def srcg_live_workspaces() -> int:
+    """Matrices that hold a srcg workspace (0 when the library was never loaded)."""
+    if _srcg_lib is None:
+        return 0
+    c = C.c_int(0)
+    _check(_srcg_lib.hpccg_hip_srcg_live_workspaces(C.byref(c)), "srcg_live_workspaces")
     return c.value
 
 

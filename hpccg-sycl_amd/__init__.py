@@ -143,471 +143,309 @@ def lib() -> C.CDLL:
     return L
 
 
+_vp, _ip, _dp, _lp = C.c_void_p, C.c_int, C.c_double, C.c_longlong
+_PI, _PD, _PV, _PL = C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)
+_units = {}  # slot -> the library of that unit, once loaded
+
+
+def _load_unit(slot: str, path: str, what: str, no_fallback: str, sig: dict) -> C.CDLL:
+    """The library of one unit, loaded on first use with its signatures bound.
+    It is linked against libhpccg_hip.so beside it, so lib() is loaded first
+    and both share one copy of the main library. what, no_fallback: "the pcg
+    library", "the preconditioned solve has no fallback" of its messages."""
+    L = _units.get(slot)
+    if L is not None:
+        return L
+    if os.environ.get("HPCCG_HIP_LIB", LIB_PATH) != LIB_PATH:
+        raise HPCCGError(f"{what} runs on the in-tree libhpccg_hip.so only (HPCCG_HIP_LIB is set)")
+    lib()
+    if not os.path.exists(path):
+        raise HPCCGError(f"{path} missing: run build() ({no_fallback})")
+    try:
+        L = C.CDLL(path)
+    except OSError as e:
+        raise HPCCGError(f"{path} does not load: {e}") from e
+    for name, (res, args) in sig.items():
+        f = getattr(L, name)
+        f.restype = res
+        f.argtypes = args
+    _units[slot] = L
+    return L
+
+
 BATCH_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_batch.so")
-_batch_lib = None
 
 
 def batch_lib() -> C.CDLL:
     """Load libhpccg_hip_batch.so (include/hpccg_hip_batch.h) on first use. It
     is linked against libhpccg_hip.so beside it, so lib() is loaded first and
     both share one copy of the main library."""
-    global _batch_lib
-    if _batch_lib is not None:
-        return _batch_lib
-    if os.environ.get("HPCCG_HIP_LIB", LIB_PATH) != LIB_PATH:
-        raise HPCCGError("the batch library runs on the in-tree libhpccg_hip.so only (HPCCG_HIP_LIB is set)")
-    lib()
-    if not os.path.exists(BATCH_LIB_PATH):
-        raise HPCCGError(f"{BATCH_LIB_PATH} missing: run build() (the batched solve has no fallback)")
-    try:
-        L = C.CDLL(BATCH_LIB_PATH)
-    except OSError as e:
-        raise HPCCGError(f"{BATCH_LIB_PATH} does not load: {e}") from e
-    vp, ip, dp, lp = C.c_void_p, C.c_int, C.c_double, C.c_longlong
-    PI, PD = C.POINTER(C.c_int), C.POINTER(C.c_double)
-    sig = {
-        "hpccg_hip_batch_abi_version": (ip, []),
-        "hpccg_hip_batch_solve_device": (ip, [vp, ip, vp, lp, vp, lp, ip, dp, PI, PD, PD]),
-        "hpccg_hip_batch_solve": (ip, [vp, ip, vp, lp, vp, lp, ip, dp, PI, PD, PD]),
-        "hpccg_hip_batch_last_trace": (ip, [vp, ip, PD, ip]),
-        "hpccg_hip_batch_sparsemv": (ip, [vp, ip, vp, lp, vp, lp]),
-        "hpccg_hip_batch_release": (ip, [vp]),
-        "hpccg_hip_batch_workspace_bytes": (ip, [vp, C.POINTER(lp)]),
-        "hpccg_hip_batch_live_workspaces": (ip, [PI]),
+    return _load_unit("batch", BATCH_LIB_PATH, "the batch library", "the batched solve has no fallback", {
+        "hpccg_hip_batch_abi_version": (_ip, []),
+        "hpccg_hip_batch_solve_device": (_ip, [_vp, _ip, _vp, _lp, _vp, _lp, _ip, _dp, _PI, _PD, _PD]),
+        "hpccg_hip_batch_solve": (_ip, [_vp, _ip, _vp, _lp, _vp, _lp, _ip, _dp, _PI, _PD, _PD]),
+        "hpccg_hip_batch_last_trace": (_ip, [_vp, _ip, _PD, _ip]),
+        "hpccg_hip_batch_sparsemv": (_ip, [_vp, _ip, _vp, _lp, _vp, _lp]),
+        "hpccg_hip_batch_release": (_ip, [_vp]),
+        "hpccg_hip_batch_workspace_bytes": (_ip, [_vp, _PL]),
+        "hpccg_hip_batch_live_workspaces": (_ip, [_PI]),
         # include/hpccg_hip_batch_group.h
-        "hpccg_hip_group_batch_abi_version": (ip, []),
-        "hpccg_hip_group_batch_solve_device": (ip, [C.POINTER(vp), ip, ip, C.POINTER(vp), C.POINTER(lp),
-                                                    C.POINTER(vp), C.POINTER(lp), ip, dp, PI, PD, PD]),
-        "hpccg_hip_group_batch_sparsemv": (ip, [C.POINTER(vp), ip, ip, C.POINTER(vp), C.POINTER(lp),
-                                                C.POINTER(vp), C.POINTER(lp)]),
-        "hpccg_hip_group_batch_last_trace": (ip, [C.POINTER(vp), ip, ip, PD, ip]),
-    }
-    for name, (res, args) in sig.items():
-        f = getattr(L, name)
-        f.restype = res
-        f.argtypes = args
-    _batch_lib = L
-    return L
+        "hpccg_hip_group_batch_abi_version": (_ip, []),
+        "hpccg_hip_group_batch_solve_device": (_ip, [_PV, _ip, _ip, _PV, _PL, _PV, _PL, _ip, _dp, _PI, _PD, _PD]),
+        "hpccg_hip_group_batch_sparsemv": (_ip, [_PV, _ip, _ip, _PV, _PL, _PV, _PL]),
+        "hpccg_hip_group_batch_last_trace": (_ip, [_PV, _ip, _ip, _PD, _ip]),
+    })
 
 
 MIXED_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_mixed.so")
-_mixed_lib = None
 
 
 def mixed_lib() -> C.CDLL:
     """Load libhpccg_hip_mixed.so (include/hpccg_hip_mixed.h) on first use. It
     is linked against libhpccg_hip.so beside it, so lib() is loaded first and
     both share one copy of the main library."""
-    global _mixed_lib
-    if _mixed_lib is not None:
-        return _mixed_lib
-    if os.environ.get("HPCCG_HIP_LIB", LIB_PATH) != LIB_PATH:
-        raise HPCCGError("the mixed library runs on the in-tree libhpccg_hip.so only (HPCCG_HIP_LIB is set)")
-    lib()
-    if not os.path.exists(MIXED_LIB_PATH):
-        raise HPCCGError(f"{MIXED_LIB_PATH} missing: run build() (the mixed solve has no fallback)")
-    try:
-        L = C.CDLL(MIXED_LIB_PATH)
-    except OSError as e:
-        raise HPCCGError(f"{MIXED_LIB_PATH} does not load: {e}") from e
-    vp, ip, dp, lp = C.c_void_p, C.c_int, C.c_double, C.c_longlong
-    PI, PD = C.POINTER(C.c_int), C.POINTER(C.c_double)
-    sig = {
-        "hpccg_hip_mixed_abi_version": (ip, []),
-        "hpccg_hip_mixed_solve_device": (ip, [vp, ip, vp, lp, vp, lp, ip, dp, ip, dp, PI, PD, PD]),
-        "hpccg_hip_mixed_solve": (ip, [vp, ip, vp, lp, vp, lp, ip, dp, ip, dp, PI, PD, PD]),
-        "hpccg_hip_mixed_sparsemv": (ip, [vp, ip, vp, lp, vp, lp]),
-        "hpccg_hip_mixed_info": (ip, [vp, C.POINTER(lp)]),
-        "hpccg_hip_mixed_last_trace": (ip, [vp, ip, PD, ip]),
-        "hpccg_hip_mixed_last_sweeps": (ip, [vp, ip, PI, PD, ip]),
-        "hpccg_hip_mixed_release": (ip, [vp]),
-        "hpccg_hip_mixed_workspace_bytes": (ip, [vp, C.POINTER(lp)]),
-        "hpccg_hip_mixed_live_workspaces": (ip, [PI]),
-    }
-    for name, (res, args) in sig.items():
-        f = getattr(L, name)
-        f.restype = res
-        f.argtypes = args
-    _mixed_lib = L
-    return L
+    return _load_unit("mixed", MIXED_LIB_PATH, "the mixed library", "the mixed solve has no fallback", {
+        "hpccg_hip_mixed_abi_version": (_ip, []),
+        "hpccg_hip_mixed_solve_device": (_ip, [_vp, _ip, _vp, _lp, _vp, _lp, _ip, _dp, _ip, _dp, _PI, _PD, _PD]),
+        "hpccg_hip_mixed_solve": (_ip, [_vp, _ip, _vp, _lp, _vp, _lp, _ip, _dp, _ip, _dp, _PI, _PD, _PD]),
+        "hpccg_hip_mixed_sparsemv": (_ip, [_vp, _ip, _vp, _lp, _vp, _lp]),
+        "hpccg_hip_mixed_info": (_ip, [_vp, _PL]),
+        "hpccg_hip_mixed_last_trace": (_ip, [_vp, _ip, _PD, _ip]),
+        "hpccg_hip_mixed_last_sweeps": (_ip, [_vp, _ip, _PI, _PD, _ip]),
+        "hpccg_hip_mixed_release": (_ip, [_vp]),
+        "hpccg_hip_mixed_workspace_bytes": (_ip, [_vp, _PL]),
+        "hpccg_hip_mixed_live_workspaces": (_ip, [_PI]),
+    })
 
 
 PCG_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_pcg.so")
-_pcg_lib = None
 
 
 def pcg_lib() -> C.CDLL:
     """Load libhpccg_hip_pcg.so (include/hpccg_hip_pcg.h) on first use. It is
     linked against libhpccg_hip.so beside it, so lib() is loaded first and both
     share one copy of the main library."""
-    global _pcg_lib
-    if _pcg_lib is not None:
-        return _pcg_lib
-    if os.environ.get("HPCCG_HIP_LIB", LIB_PATH) != LIB_PATH:
-        raise HPCCGError("the pcg library runs on the in-tree libhpccg_hip.so only (HPCCG_HIP_LIB is set)")
-    lib()
-    if not os.path.exists(PCG_LIB_PATH):
-        raise HPCCGError(f"{PCG_LIB_PATH} missing: run build() (the preconditioned solve has no fallback)")
-    try:
-        L = C.CDLL(PCG_LIB_PATH)
-    except OSError as e:
-        raise HPCCGError(f"{PCG_LIB_PATH} does not load: {e}") from e
-    vp, ip, dp, lp = C.c_void_p, C.c_int, C.c_double, C.c_longlong
-    PI, PD = C.POINTER(C.c_int), C.POINTER(C.c_double)
-    sig = {
-        "hpccg_hip_pcg_abi_version": (ip, []),
-        "hpccg_hip_pcg_solve_device": (ip, [vp, ip, vp, lp, vp, lp, vp, ip, dp, PI, PD, PD]),
-        "hpccg_hip_pcg_solve": (ip, [vp, ip, vp, lp, vp, lp, vp, ip, dp, PI, PD, PD]),
-        "hpccg_hip_pcg_diagonal": (ip, [vp, vp]),
-        "hpccg_hip_pcg_last_trace": (ip, [vp, ip, PD, ip]),
-        "hpccg_hip_pcg_release": (ip, [vp]),
-        "hpccg_hip_pcg_workspace_bytes": (ip, [vp, C.POINTER(lp)]),
-        "hpccg_hip_pcg_live_workspaces": (ip, [PI]),
-    }
-    for name, (res, args) in sig.items():
-        f = getattr(L, name)
-        f.restype = res
-        f.argtypes = args
-    _pcg_lib = L
-    return L
+    return _load_unit("pcg", PCG_LIB_PATH, "the pcg library", "the preconditioned solve has no fallback", {
+        "hpccg_hip_pcg_abi_version": (_ip, []),
+        "hpccg_hip_pcg_solve_device": (_ip, [_vp, _ip, _vp, _lp, _vp, _lp, _vp, _ip, _dp, _PI, _PD, _PD]),
+        "hpccg_hip_pcg_solve": (_ip, [_vp, _ip, _vp, _lp, _vp, _lp, _vp, _ip, _dp, _PI, _PD, _PD]),
+        "hpccg_hip_pcg_diagonal": (_ip, [_vp, _vp]),
+        "hpccg_hip_pcg_last_trace": (_ip, [_vp, _ip, _PD, _ip]),
+        "hpccg_hip_pcg_release": (_ip, [_vp]),
+        "hpccg_hip_pcg_workspace_bytes": (_ip, [_vp, _PL]),
+        "hpccg_hip_pcg_live_workspaces": (_ip, [_PI]),
+    })
 
 
 SRCG_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_srcg.so")
-_srcg_lib = None
 
 
 def srcg_lib() -> C.CDLL:
     """Load libhpccg_hip_srcg.so (include/hpccg_hip_srcg.h) on first use. It is
     linked against libhpccg_hip.so beside it, so lib() is loaded first and both
     share one copy of the main library."""
-    global _srcg_lib
-    if _srcg_lib is not None:
-        return _srcg_lib
-    if os.environ.get("HPCCG_HIP_LIB", LIB_PATH) != LIB_PATH:
-        raise HPCCGError("the srcg library runs on the in-tree libhpccg_hip.so only (HPCCG_HIP_LIB is set)")
-    lib()
-    if not os.path.exists(SRCG_LIB_PATH):
-        raise HPCCGError(f"{SRCG_LIB_PATH} missing: run build() (the single-reduction solve has no fallback)")
-    try:
-        L = C.CDLL(SRCG_LIB_PATH)
-    except OSError as e:
-        raise HPCCGError(f"{SRCG_LIB_PATH} does not load: {e}") from e
-    vp, ip, dp, lp = C.c_void_p, C.c_int, C.c_double, C.c_longlong
-    PI, PD = C.POINTER(C.c_int), C.POINTER(C.c_double)
-    sig = {
-        "hpccg_hip_srcg_abi_version": (ip, []),
-        "hpccg_hip_srcg_solve_device": (ip, [vp, ip, vp, lp, vp, lp, vp, ip, dp, PI, PD, PD]),
-        "hpccg_hip_srcg_solve": (ip, [vp, ip, vp, lp, vp, lp, vp, ip, dp, PI, PD, PD]),
-        "hpccg_hip_srcg_last_trace": (ip, [vp, ip, PD, ip]),
-        "hpccg_hip_srcg_release": (ip, [vp]),
-        "hpccg_hip_srcg_workspace_bytes": (ip, [vp, C.POINTER(lp)]),
-        "hpccg_hip_srcg_live_workspaces": (ip, [PI]),
-    }
-    for name, (res, args) in sig.items():
-        f = getattr(L, name)
-        f.restype = res
-        f.argtypes = args
-    _srcg_lib = L
-    return L
+    return _load_unit("srcg", SRCG_LIB_PATH, "the srcg library", "the single-reduction solve has no fallback", {
+        "hpccg_hip_srcg_abi_version": (_ip, []),
+        "hpccg_hip_srcg_solve_device": (_ip, [_vp, _ip, _vp, _lp, _vp, _lp, _vp, _ip, _dp, _PI, _PD, _PD]),
+        "hpccg_hip_srcg_solve": (_ip, [_vp, _ip, _vp, _lp, _vp, _lp, _vp, _ip, _dp, _PI, _PD, _PD]),
+        "hpccg_hip_srcg_last_trace": (_ip, [_vp, _ip, _PD, _ip]),
+        "hpccg_hip_srcg_release": (_ip, [_vp]),
+        "hpccg_hip_srcg_workspace_bytes": (_ip, [_vp, _PL]),
+        "hpccg_hip_srcg_live_workspaces": (_ip, [_PI]),
+    })
 
 
 PCG_GROUP_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_pcg_group.so")
-_pcg_group_lib = None
 
 
 def pcg_group_lib() -> C.CDLL:
     """Load libhpccg_hip_pcg_group.so (include/hpccg_hip_pcg_group.h) on first
     use. It is linked against libhpccg_hip.so beside it, so lib() is loaded
     first and both share one copy of the main library."""
-    global _pcg_group_lib
-    if _pcg_group_lib is not None:
-        return _pcg_group_lib
-    if os.environ.get("HPCCG_HIP_LIB", LIB_PATH) != LIB_PATH:
-        raise HPCCGError("the group pcg library runs on the in-tree libhpccg_hip.so only (HPCCG_HIP_LIB is set)")
-    lib()
-    if not os.path.exists(PCG_GROUP_LIB_PATH):
-        raise HPCCGError(f"{PCG_GROUP_LIB_PATH} missing: run build() (the group preconditioned solve has no "
-                         "fallback)")
-    try:
-        L = C.CDLL(PCG_GROUP_LIB_PATH)
-    except OSError as e:
-        raise HPCCGError(f"{PCG_GROUP_LIB_PATH} does not load: {e}") from e
-    vp, ip, dp, lp = C.c_void_p, C.c_int, C.c_double, C.c_longlong
-    PI, PD, PV, PL = C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(vp), C.POINTER(lp)
-    sig = {
-        "hpccg_hip_group_pcg_abi_version": (ip, []),
-        "hpccg_hip_group_pcg_solve_device": (ip, [PV, ip, ip, PV, PL, PV, PL, PV, ip, dp, PI, PD, PD]),
-        "hpccg_hip_group_pcg_diagonal": (ip, [PV, ip, PV]),
-        "hpccg_hip_group_pcg_last_trace": (ip, [PV, ip, ip, PD, ip]),
-        "hpccg_hip_group_pcg_release": (ip, [vp]),
-        "hpccg_hip_group_pcg_workspace_bytes": (ip, [vp, PL]),
-        "hpccg_hip_group_pcg_live_workspaces": (ip, [PI]),
-    }
-    for name, (res, args) in sig.items():
-        f = getattr(L, name)
-        f.restype = res
-        f.argtypes = args
-    _pcg_group_lib = L
-    return L
+    return _load_unit("pcg_group", PCG_GROUP_LIB_PATH, "the group pcg library", "the group preconditioned solve has no fallback", {
+        "hpccg_hip_group_pcg_abi_version": (_ip, []),
+        "hpccg_hip_group_pcg_solve_device": (_ip, [_PV, _ip, _ip, _PV, _PL, _PV, _PL, _PV, _ip, _dp, _PI, _PD, _PD]),
+        "hpccg_hip_group_pcg_diagonal": (_ip, [_PV, _ip, _PV]),
+        "hpccg_hip_group_pcg_last_trace": (_ip, [_PV, _ip, _ip, _PD, _ip]),
+        "hpccg_hip_group_pcg_release": (_ip, [_vp]),
+        "hpccg_hip_group_pcg_workspace_bytes": (_ip, [_vp, _PL]),
+        "hpccg_hip_group_pcg_live_workspaces": (_ip, [_PI]),
+    })
 
 
 POLY_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_poly.so")
-_poly_lib = None
 
 
 def poly_lib() -> C.CDLL:
     """Load libhpccg_hip_poly.so (include/hpccg_hip_poly.h) on first use. It is
     linked against libhpccg_hip.so beside it, so lib() is loaded first and both
     share one copy of the main library."""
-    global _poly_lib
-    if _poly_lib is not None:
-        return _poly_lib
-    if os.environ.get("HPCCG_HIP_LIB", LIB_PATH) != LIB_PATH:
-        raise HPCCGError("the poly library runs on the in-tree libhpccg_hip.so only (HPCCG_HIP_LIB is set)")
-    lib()
-    if not os.path.exists(POLY_LIB_PATH):
-        raise HPCCGError(f"{POLY_LIB_PATH} missing: run build() (the polynomial solve has no fallback)")
-    try:
-        L = C.CDLL(POLY_LIB_PATH)
-    except OSError as e:
-        raise HPCCGError(f"{POLY_LIB_PATH} does not load: {e}") from e
-    vp, ip, dp, lp = C.c_void_p, C.c_int, C.c_double, C.c_longlong
-    PI, PD = C.POINTER(C.c_int), C.POINTER(C.c_double)
-    sig = {
-        "hpccg_hip_poly_abi_version": (ip, []),
-        "hpccg_hip_poly_solve_device": (ip, [vp, ip, vp, lp, vp, lp, vp, ip, dp, dp, ip, dp, PI, PD, PD]),
-        "hpccg_hip_poly_solve": (ip, [vp, ip, vp, lp, vp, lp, vp, ip, dp, dp, ip, dp, PI, PD, PD]),
-        "hpccg_hip_poly_bound": (ip, [vp, vp, PD]),
-        "hpccg_hip_poly_last_spectrum": (ip, [vp, PD, PD]),
-        "hpccg_hip_poly_last_trace": (ip, [vp, ip, PD, ip]),
-        "hpccg_hip_poly_release": (ip, [vp]),
-        "hpccg_hip_poly_workspace_bytes": (ip, [vp, C.POINTER(lp)]),
-        "hpccg_hip_poly_live_workspaces": (ip, [PI]),
-    }
-    for name, (res, args) in sig.items():
-        f = getattr(L, name)
-        f.restype = res
-        f.argtypes = args
-    _poly_lib = L
-    return L
+    return _load_unit("poly", POLY_LIB_PATH, "the poly library", "the polynomial solve has no fallback", {
+        "hpccg_hip_poly_abi_version": (_ip, []),
+        "hpccg_hip_poly_solve_device": (_ip, [_vp, _ip, _vp, _lp, _vp, _lp, _vp, _ip, _dp, _dp, _ip, _dp, _PI, _PD, _PD]),
+        "hpccg_hip_poly_solve": (_ip, [_vp, _ip, _vp, _lp, _vp, _lp, _vp, _ip, _dp, _dp, _ip, _dp, _PI, _PD, _PD]),
+        "hpccg_hip_poly_bound": (_ip, [_vp, _vp, _PD]),
+        "hpccg_hip_poly_last_spectrum": (_ip, [_vp, _PD, _PD]),
+        "hpccg_hip_poly_last_trace": (_ip, [_vp, _ip, _PD, _ip]),
+        "hpccg_hip_poly_release": (_ip, [_vp]),
+        "hpccg_hip_poly_workspace_bytes": (_ip, [_vp, _PL]),
+        "hpccg_hip_poly_live_workspaces": (_ip, [_PI]),
+    })
 
 
 POLY_GROUP_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_poly_group.so")
-_poly_group_lib = None
 
 
 def poly_group_lib() -> C.CDLL:
     """Load libhpccg_hip_poly_group.so (include/hpccg_hip_poly_group.h) on first
     use. It is linked against libhpccg_hip.so beside it, so lib() is loaded
     first and both share one copy of the main library."""
-    global _poly_group_lib
-    if _poly_group_lib is not None:
-        return _poly_group_lib
-    if os.environ.get("HPCCG_HIP_LIB", LIB_PATH) != LIB_PATH:
-        raise HPCCGError("the group poly library runs on the in-tree libhpccg_hip.so only (HPCCG_HIP_LIB is set)")
-    lib()
-    if not os.path.exists(POLY_GROUP_LIB_PATH):
-        raise HPCCGError(f"{POLY_GROUP_LIB_PATH} missing: run build() (the group polynomial solve has no fallback)")
-    try:
-        L = C.CDLL(POLY_GROUP_LIB_PATH)
-    except OSError as e:
-        raise HPCCGError(f"{POLY_GROUP_LIB_PATH} does not load: {e}") from e
-    vp, ip, dp, lp = C.c_void_p, C.c_int, C.c_double, C.c_longlong
-    PI, PD, PV, PL = C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(vp), C.POINTER(lp)
-    sig = {
-        "hpccg_hip_group_poly_abi_version": (ip, []),
-        "hpccg_hip_group_poly_solve_device": (ip, [PV, ip, ip, PV, PL, PV, PL, PV, ip, dp, dp, ip, dp, PI, PD, PD]),
-        "hpccg_hip_group_poly_bound": (ip, [PV, ip, PV, PD]),
-        "hpccg_hip_group_poly_last_spectrum": (ip, [PV, ip, PD, PD]),
-        "hpccg_hip_group_poly_last_trace": (ip, [PV, ip, ip, PD, ip]),
-        "hpccg_hip_group_poly_release": (ip, [vp]),
-        "hpccg_hip_group_poly_workspace_bytes": (ip, [vp, PL]),
-        "hpccg_hip_group_poly_live_workspaces": (ip, [PI]),
-    }
-    for name, (res, args) in sig.items():
-        f = getattr(L, name)
-        f.restype = res
-        f.argtypes = args
-    _poly_group_lib = L
-    return L
+    return _load_unit("poly_group", POLY_GROUP_LIB_PATH, "the group poly library", "the group polynomial solve has no fallback", {
+        "hpccg_hip_group_poly_abi_version": (_ip, []),
+        "hpccg_hip_group_poly_solve_device": (_ip, [_PV, _ip, _ip, _PV, _PL, _PV, _PL, _PV, _ip, _dp, _dp, _ip, _dp, _PI, _PD, _PD]),
+        "hpccg_hip_group_poly_bound": (_ip, [_PV, _ip, _PV, _PD]),
+        "hpccg_hip_group_poly_last_spectrum": (_ip, [_PV, _ip, _PD, _PD]),
+        "hpccg_hip_group_poly_last_trace": (_ip, [_PV, _ip, _ip, _PD, _ip]),
+        "hpccg_hip_group_poly_release": (_ip, [_vp]),
+        "hpccg_hip_group_poly_workspace_bytes": (_ip, [_vp, _PL]),
+        "hpccg_hip_group_poly_live_workspaces": (_ip, [_PI]),
+    })
 
 
 POLY32_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_poly32.so")
-_poly32_lib = None
 
 
 def poly32_lib() -> C.CDLL:
     """Load libhpccg_hip_poly32.so (include/hpccg_hip_poly32.h) on first use. It
     is linked against libhpccg_hip.so beside it, so lib() is loaded first and
     both share one copy of the main library."""
-    global _poly32_lib
-    if _poly32_lib is not None:
-        return _poly32_lib
-    if os.environ.get("HPCCG_HIP_LIB", LIB_PATH) != LIB_PATH:
-        raise HPCCGError("the poly32 library runs on the in-tree libhpccg_hip.so only (HPCCG_HIP_LIB is set)")
-    lib()
-    if not os.path.exists(POLY32_LIB_PATH):
-        raise HPCCGError(f"{POLY32_LIB_PATH} missing: run build() (the fp32-image polynomial solve has no fallback)")
-    try:
-        L = C.CDLL(POLY32_LIB_PATH)
-    except OSError as e:
-        raise HPCCGError(f"{POLY32_LIB_PATH} does not load: {e}") from e
-    vp, ip, dp, lp = C.c_void_p, C.c_int, C.c_double, C.c_longlong
-    PI, PD = C.POINTER(C.c_int), C.POINTER(C.c_double)
-    sig = {
-        "hpccg_hip_poly32_abi_version": (ip, []),
-        "hpccg_hip_poly32_solve_device": (ip, [vp, ip, vp, lp, vp, lp, vp, ip, dp, dp, ip, dp, PI, PD, PD]),
-        "hpccg_hip_poly32_solve": (ip, [vp, ip, vp, lp, vp, lp, vp, ip, dp, dp, ip, dp, PI, PD, PD]),
-        "hpccg_hip_poly32_bound": (ip, [vp, vp, PD]),
-        "hpccg_hip_poly32_last_spectrum": (ip, [vp, PD, PD]),
-        "hpccg_hip_poly32_last_trace": (ip, [vp, ip, PD, ip]),
-        "hpccg_hip_poly32_info": (ip, [vp, C.POINTER(lp)]),
-        "hpccg_hip_poly32_release": (ip, [vp]),
-        "hpccg_hip_poly32_workspace_bytes": (ip, [vp, C.POINTER(lp)]),
-        "hpccg_hip_poly32_live_workspaces": (ip, [PI]),
-    }
-    for name, (res, args) in sig.items():
-        f = getattr(L, name)
-        f.restype = res
-        f.argtypes = args
-    _poly32_lib = L
-    return L
+    return _load_unit("poly32", POLY32_LIB_PATH, "the poly32 library", "the fp32-image polynomial solve has no fallback", {
+        "hpccg_hip_poly32_abi_version": (_ip, []),
+        "hpccg_hip_poly32_solve_device": (_ip, [_vp, _ip, _vp, _lp, _vp, _lp, _vp, _ip, _dp, _dp, _ip, _dp, _PI, _PD, _PD]),
+        "hpccg_hip_poly32_solve": (_ip, [_vp, _ip, _vp, _lp, _vp, _lp, _vp, _ip, _dp, _dp, _ip, _dp, _PI, _PD, _PD]),
+        "hpccg_hip_poly32_bound": (_ip, [_vp, _vp, _PD]),
+        "hpccg_hip_poly32_last_spectrum": (_ip, [_vp, _PD, _PD]),
+        "hpccg_hip_poly32_last_trace": (_ip, [_vp, _ip, _PD, _ip]),
+        "hpccg_hip_poly32_info": (_ip, [_vp, _PL]),
+        "hpccg_hip_poly32_release": (_ip, [_vp]),
+        "hpccg_hip_poly32_workspace_bytes": (_ip, [_vp, _PL]),
+        "hpccg_hip_poly32_live_workspaces": (_ip, [_PI]),
+    })
 
 
 POLY32_GROUP_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_poly32_group.so")
-_poly32_group_lib = None
 
 
 def poly32_group_lib() -> C.CDLL:
     """Load libhpccg_hip_poly32_group.so (include/hpccg_hip_poly32_group.h) on
     first use. It is linked against libhpccg_hip.so beside it, so lib() is
     loaded first and both share one copy of the main library."""
-    global _poly32_group_lib
-    if _poly32_group_lib is not None:
-        return _poly32_group_lib
-    if os.environ.get("HPCCG_HIP_LIB", LIB_PATH) != LIB_PATH:
-        raise HPCCGError("the group poly32 library runs on the in-tree libhpccg_hip.so only (HPCCG_HIP_LIB is set)")
-    lib()
-    if not os.path.exists(POLY32_GROUP_LIB_PATH):
-        raise HPCCGError(f"{POLY32_GROUP_LIB_PATH} missing: run build() (the group fp32-image polynomial solve has "
-                         "no fallback)")
-    try:
-        L = C.CDLL(POLY32_GROUP_LIB_PATH)
-    except OSError as e:
-        raise HPCCGError(f"{POLY32_GROUP_LIB_PATH} does not load: {e}") from e
-    vp, ip, dp, lp = C.c_void_p, C.c_int, C.c_double, C.c_longlong
-    PI, PD, PV, PL = C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(vp), C.POINTER(lp)
-    sig = {
-        "hpccg_hip_group_poly32_abi_version": (ip, []),
-        "hpccg_hip_group_poly32_solve_device": (ip, [PV, ip, ip, PV, PL, PV, PL, PV, ip, dp, dp, ip, dp, PI, PD, PD]),
-        "hpccg_hip_group_poly32_bound": (ip, [PV, ip, PV, PD]),
-        "hpccg_hip_group_poly32_last_spectrum": (ip, [PV, ip, PD, PD]),
-        "hpccg_hip_group_poly32_last_trace": (ip, [PV, ip, ip, PD, ip]),
-        "hpccg_hip_group_poly32_info": (ip, [PV, ip, PL]),
-        "hpccg_hip_group_poly32_release": (ip, [vp]),
-        "hpccg_hip_group_poly32_workspace_bytes": (ip, [vp, PL]),
-        "hpccg_hip_group_poly32_live_workspaces": (ip, [PI]),
-    }
-    for name, (res, args) in sig.items():
-        f = getattr(L, name)
-        f.restype = res
-        f.argtypes = args
-    _poly32_group_lib = L
-    return L
+    return _load_unit("poly32_group", POLY32_GROUP_LIB_PATH, "the group poly32 library", "the group fp32-image polynomial solve has no fallback", {
+        "hpccg_hip_group_poly32_abi_version": (_ip, []),
+        "hpccg_hip_group_poly32_solve_device": (_ip, [_PV, _ip, _ip, _PV, _PL, _PV, _PL, _PV, _ip, _dp, _dp, _ip, _dp, _PI, _PD, _PD]),
+        "hpccg_hip_group_poly32_bound": (_ip, [_PV, _ip, _PV, _PD]),
+        "hpccg_hip_group_poly32_last_spectrum": (_ip, [_PV, _ip, _PD, _PD]),
+        "hpccg_hip_group_poly32_last_trace": (_ip, [_PV, _ip, _ip, _PD, _ip]),
+        "hpccg_hip_group_poly32_info": (_ip, [_PV, _ip, _PL]),
+        "hpccg_hip_group_poly32_release": (_ip, [_vp]),
+        "hpccg_hip_group_poly32_workspace_bytes": (_ip, [_vp, _PL]),
+        "hpccg_hip_group_poly32_live_workspaces": (_ip, [_PI]),
+    })
+
+
+def _declared(header: str, pattern: str) -> list[str]:
+    """The names pattern finds in include/<header>, sorted."""
+    import re
+    with open(os.path.join(ROOT, "include", header)) as f:
+        return sorted(set(re.findall(pattern, f.read())))
 
 
 def group_poly32_exported_symbols() -> list[str]:
     """Functions include/hpccg_hip_poly32_group.h declares (checked by the CPU suite)."""
-    import re
-    with open(os.path.join(ROOT, "include", "hpccg_hip_poly32_group.h")) as f:
-        text = f.read()
-    return sorted(set(re.findall(r"\b(hpccg_hip_group_poly32_\w+)\s*\(", text)))
+    return _declared("hpccg_hip_poly32_group.h", r"\b(hpccg_hip_group_poly32_\w+)\s*\(")
 
 
 def poly32_exported_symbols() -> list[str]:
     """Functions include/hpccg_hip_poly32.h declares (checked by the CPU suite)."""
-    import re
-    with open(os.path.join(ROOT, "include", "hpccg_hip_poly32.h")) as f:
-        text = f.read()
-    return sorted(set(re.findall(r"\b(hpccg_hip_poly32_\w+)\s*\(", text)))
+    return _declared("hpccg_hip_poly32.h", r"\b(hpccg_hip_poly32_\w+)\s*\(")
 
 
 def group_poly_exported_symbols() -> list[str]:
     """Functions include/hpccg_hip_poly_group.h declares (checked by the CPU suite)."""
-    import re
-    with open(os.path.join(ROOT, "include", "hpccg_hip_poly_group.h")) as f:
-        text = f.read()
-    return sorted(set(re.findall(r"\b(hpccg_hip_group_poly_\w+)\s*\(", text)))
+    return _declared("hpccg_hip_poly_group.h", r"\b(hpccg_hip_group_poly_\w+)\s*\(")
 
 
 def poly_exported_symbols() -> list[str]:
     """Functions include/hpccg_hip_poly.h declares (checked by the CPU suite)."""
-    import re
-    with open(os.path.join(ROOT, "include", "hpccg_hip_poly.h")) as f:
-        text = f.read()
-    return sorted(set(re.findall(r"\b(hpccg_hip_poly_\w+)\s*\(", text)))
+    return _declared("hpccg_hip_poly.h", r"\b(hpccg_hip_poly_\w+)\s*\(")
 
 
 def group_pcg_exported_symbols() -> list[str]:
     """Functions include/hpccg_hip_pcg_group.h declares (checked by the CPU suite)."""
-    import re
-    with open(os.path.join(ROOT, "include", "hpccg_hip_pcg_group.h")) as f:
-        text = f.read()
-    return sorted(set(re.findall(r"\b(hpccg_hip_group_pcg_\w+)\s*\(", text)))
+    return _declared("hpccg_hip_pcg_group.h", r"\b(hpccg_hip_group_pcg_\w+)\s*\(")
 
 
 def pcg_exported_symbols() -> list[str]:
     """Functions include/hpccg_hip_pcg.h declares (checked by the CPU suite)."""
-    import re
-    with open(os.path.join(ROOT, "include", "hpccg_hip_pcg.h")) as f:
-        text = f.read()
-    return sorted(set(re.findall(r"\b(hpccg_hip_pcg_\w+)\s*\(", text)))
+    return _declared("hpccg_hip_pcg.h", r"\b(hpccg_hip_pcg_\w+)\s*\(")
 
 
 def srcg_exported_symbols() -> list[str]:
     """Functions include/hpccg_hip_srcg.h declares (checked by the CPU suite)."""
-    import re
-    with open(os.path.join(ROOT, "include", "hpccg_hip_srcg.h")) as f:
-        text = f.read()
-    return sorted(set(re.findall(r"\b(hpccg_hip_srcg_\w+)\s*\(", text)))
+    return _declared("hpccg_hip_srcg.h", r"\b(hpccg_hip_srcg_\w+)\s*\(")
 
 
 def mixed_exported_symbols() -> list[str]:
     """Functions include/hpccg_hip_mixed.h declares (checked by the CPU suite)."""
-    import re
-    with open(os.path.join(ROOT, "include", "hpccg_hip_mixed.h")) as f:
-        text = f.read()
-    return sorted(set(re.findall(r"\b(hpccg_hip_mixed_\w+)\s*\(", text)))
+    return _declared("hpccg_hip_mixed.h", r"\b(hpccg_hip_mixed_\w+)\s*\(")
 
 
 def batch_exported_symbols() -> list[str]:
     """Functions include/hpccg_hip_batch.h declares (checked by the CPU suite)."""
-    import re
-    with open(os.path.join(ROOT, "include", "hpccg_hip_batch.h")) as f:
-        text = f.read()
-    return sorted(set(re.findall(r"\b(hpccg_hip_batch_\w+)\s*\(", text)))
+    return _declared("hpccg_hip_batch.h", r"\b(hpccg_hip_batch_\w+)\s*\(")
 
 
 def group_batch_exported_symbols() -> list[str]:
     """Functions include/hpccg_hip_batch_group.h declares (checked by the CPU suite)."""
-    import re
-    with open(os.path.join(ROOT, "include", "hpccg_hip_batch_group.h")) as f:
-        text = f.read()
-    return sorted(set(re.findall(r"\b(hpccg_hip_group_batch_\w+)\s*\(", text)))
+    return _declared("hpccg_hip_batch_group.h", r"\b(hpccg_hip_group_batch_\w+)\s*\(")
 
 
 def exported_symbols() -> list[str]:
     """Functions include/hpccg_hip.h declares (checked by the CPU suite)."""
-    import re
-    with open(os.path.join(ROOT, "include", "hpccg_hip.h")) as f:
-        text = f.read()
-    return sorted(set(re.findall(r"\b(hpccg_\w+)\s*\(", text)))
+    return _declared("hpccg_hip.h", r"\b(hpccg_\w+)\s*\(")
 
 
 def _check(rc: int, what: str) -> None:
     if rc != 0:
         msg = lib().hpccg_hip_last_error().decode(errors="replace")
         raise HPCCGError(f"{what} failed ({rc}): {msg}")
+
+
+def _live(slot: str, name: str) -> int:
+    """hpccg_hip_<name>'s count; 0 when the unit's library was never loaded."""
+    L = _units.get(slot)
+    if L is None:
+        return 0
+    c = C.c_int(0)
+    _check(getattr(L, "hpccg_hip_" + name)(C.byref(c)), name)
+    return c.value
+
+
+def _workspace_bytes(slot: str, name: str, h) -> int:
+    """hpccg_hip_<name>'s bytes of matrix h; 0 when the unit's library was never loaded."""
+    L = _units.get(slot)
+    if L is None:
+        return 0
+    v = C.c_longlong(0)
+    _check(getattr(L, "hpccg_hip_" + name)(h, C.byref(v)), name)
+    return v.value
+
+
+def _release(slot: str, name: str, h) -> None:
+    """hpccg_hip_<name> on matrix h, where there is one and the unit's library was ever loaded."""
+    L = _units.get(slot)
+    if h and L is not None:
+        _check(getattr(L, "hpccg_hip_" + name)(h), name)
 
 
 def _ptr(a) -> int:
@@ -850,15 +688,10 @@ class Matrix:
 
     def batch_release(self) -> None:
         """Free this matrix's batch workspace now (close() does it too)."""
-        if self.h and _batch_lib is not None:
-            _check(_batch_lib.hpccg_hip_batch_release(self.h), "batch_release")
+        _release("batch", "batch_release", self.h)
 
     def batch_workspace_bytes(self) -> int:
-        if _batch_lib is None:
-            return 0
-        v = C.c_longlong(0)
-        _check(_batch_lib.hpccg_hip_batch_workspace_bytes(self.h, C.byref(v)), "batch_workspace_bytes")
-        return v.value
+        return _workspace_bytes("batch", "batch_workspace_bytes", self.h)
 
     def mixed_info(self) -> dict:
         """The fp32 image of this matrix (built on first use): exact (every
@@ -892,15 +725,10 @@ class Matrix:
 
     def mixed_release(self) -> None:
         """Free this matrix's mixed workspace and fp32 image now (close() does it too)."""
-        if self.h and _mixed_lib is not None:
-            _check(_mixed_lib.hpccg_hip_mixed_release(self.h), "mixed_release")
+        _release("mixed", "mixed_release", self.h)
 
     def mixed_workspace_bytes(self) -> int:
-        if _mixed_lib is None:
-            return 0
-        v = C.c_longlong(0)
-        _check(_mixed_lib.hpccg_hip_mixed_workspace_bytes(self.h, C.byref(v)), "mixed_workspace_bytes")
-        return v.value
+        return _workspace_bytes("mixed", "mixed_workspace_bytes", self.h)
 
     def diagonal_pcg(self) -> np.ndarray:
         """The matrix's diagonal as the preconditioned solve reads it from the
@@ -921,15 +749,10 @@ class Matrix:
 
     def pcg_release(self) -> None:
         """Free this matrix's pcg workspace (with its cached 1 / a_ii) now (close() does it too)."""
-        if self.h and _pcg_lib is not None:
-            _check(_pcg_lib.hpccg_hip_pcg_release(self.h), "pcg_release")
+        _release("pcg", "pcg_release", self.h)
 
     def pcg_workspace_bytes(self) -> int:
-        if _pcg_lib is None:
-            return 0
-        v = C.c_longlong(0)
-        _check(_pcg_lib.hpccg_hip_pcg_workspace_bytes(self.h, C.byref(v)), "pcg_workspace_bytes")
-        return v.value
+        return _workspace_bytes("pcg", "pcg_workspace_bytes", self.h)
 
     def last_trace_srcg(self, col: int, cap: int = 100000) -> np.ndarray:
         """Residual trace (norm of r) of column col of the last HPCCG_srcg on this matrix."""
@@ -941,15 +764,10 @@ class Matrix:
 
     def srcg_release(self) -> None:
         """Free this matrix's srcg workspace (with its cached 1 / a_ii) now (close() does it too)."""
-        if self.h and _srcg_lib is not None:
-            _check(_srcg_lib.hpccg_hip_srcg_release(self.h), "srcg_release")
+        _release("srcg", "srcg_release", self.h)
 
     def srcg_workspace_bytes(self) -> int:
-        if _srcg_lib is None:
-            return 0
-        v = C.c_longlong(0)
-        _check(_srcg_lib.hpccg_hip_srcg_workspace_bytes(self.h, C.byref(v)), "srcg_workspace_bytes")
-        return v.value
+        return _workspace_bytes("srcg", "srcg_workspace_bytes", self.h)
 
     def last_trace_poly(self, col: int, cap: int = 100000) -> np.ndarray:
         """Residual trace (norm of r) of column col of the last HPCCG_poly on this matrix."""
@@ -967,15 +785,10 @@ class Matrix:
 
     def poly_release(self) -> None:
         """Free this matrix's poly workspace (with its cached 1 / a_ii and bound) now (close() does it too)."""
-        if self.h and _poly_lib is not None:
-            _check(_poly_lib.hpccg_hip_poly_release(self.h), "poly_release")
+        _release("poly", "poly_release", self.h)
 
     def poly_workspace_bytes(self) -> int:
-        if _poly_lib is None:
-            return 0
-        v = C.c_longlong(0)
-        _check(_poly_lib.hpccg_hip_poly_workspace_bytes(self.h, C.byref(v)), "poly_workspace_bytes")
-        return v.value
+        return _workspace_bytes("poly", "poly_workspace_bytes", self.h)
 
     def last_trace_poly32(self, col: int, cap: int = 100000) -> np.ndarray:
         """Residual trace (norm of r) of column col of the last HPCCG_poly32 on this matrix."""
@@ -993,15 +806,10 @@ class Matrix:
 
     def poly32_release(self) -> None:
         """Free this matrix's poly32 workspace and fp32 image now (close() does it too)."""
-        if self.h and _poly32_lib is not None:
-            _check(_poly32_lib.hpccg_hip_poly32_release(self.h), "poly32_release")
+        _release("poly32", "poly32_release", self.h)
 
     def poly32_workspace_bytes(self) -> int:
-        if _poly32_lib is None:
-            return 0
-        v = C.c_longlong(0)
-        _check(_poly32_lib.hpccg_hip_poly32_workspace_bytes(self.h, C.byref(v)), "poly32_workspace_bytes")
-        return v.value
+        return _workspace_bytes("poly32", "poly32_workspace_bytes", self.h)
 
     def close(self):
         # (a batch workspace goes with the matrix: the library's destroy hook,
@@ -1113,11 +921,7 @@ def HPC_sparsemv_batch(M: Matrix, X, Y, nrhs=None, ldx=None, ldy=None) -> int:
 
 def batch_live_workspaces() -> int:
     """Matrices that hold a batch workspace (0 when the library was never loaded)."""
-    if _batch_lib is None:
-        return 0
-    c = C.c_int(0)
-    _check(_batch_lib.hpccg_hip_batch_live_workspaces(C.byref(c)), "batch_live_workspaces")
-    return c.value
+    return _live("batch", "batch_live_workspaces")
 
 
 
@@ -1176,105 +980,11 @@ def HPC_sparsemv_mixed(M: Matrix, X, Y, nrhs=None, ldx=None, ldy=None) -> int:
 
 def mixed_live_workspaces() -> int:
     """Matrices that hold a mixed workspace (0 when the library was never loaded)."""
-    if _mixed_lib is None:
-        return 0
-    c = C.c_int(0)
-    _check(_mixed_lib.hpccg_hip_mixed_live_workspaces(C.byref(c)), "mixed_live_workspaces")
-    return c.value
+    return _live("mixed", "mixed_live_workspaces")
 
 
 # ---------------------------------------------------------------------------
 # diagonally preconditioned solve (include/hpccg_hip_pcg.h)
-# ---------------------------------------------------------------------------
-def HPCCG_pcg(M: Matrix, B, X, max_iter: int = 500, tolerance: float = 0.0, minv=None, device=False, nrhs=None,
-              ldb=None, ldx=None):
-    """nrhs preconditioned CG solves against M with M^-1 = diag(minv)
-    (hpccg_hip_pcg_solve[_device]); minv None is Jacobi, 1 / a_ii. The loop
-    test, niters and normr are on the 2-norm of r, as in HPCCG. B, X: as
-    HPCCG_batch (a 1-D array or tensor is one column); minv: nrow entries, all
-    finite and > 0 -- numpy on the host or, with device=True, a tensor / device
-    pointer. X is updated in place. Returns (ierr, niters[nrhs], normr[nrhs],
-    times)."""
-    L = pcg_lib()
-    B, X = _one_column(B, "B"), _one_column(X, "X")
-    bp, nb, ldb_ = _cols(B, nrhs, ldb, "B")
-    xp, nx_, ldx_ = _cols(X, nrhs, ldx, "X")
-    if nb != nx_:
-        raise HPCCGError(f"B holds {nb} columns, X {nx_}")
-    if not device and not (isinstance(B, np.ndarray) and isinstance(X, np.ndarray)):
-        raise HPCCGError("host solve: B and X are numpy arrays")
-    mp, keep = None, None
-    if minv is not None:
-        nrow = int(M.info()["nrow"])
-        if device:
-            if not isinstance(minv, int) and (minv.dim() != 1 or minv.shape[0] < nrow or
-                                              (minv.shape[0] > 1 and minv.stride(0) != 1)):
-                raise HPCCGError(f"minv: a contiguous 1-D tensor of {nrow} entries")
-            mp = _ptr(minv)
-        else:
-            keep = np.ascontiguousarray(minv, np.float64)
-            if keep.ndim != 1 or keep.shape[0] < nrow:
-                raise HPCCGError(f"minv: a 1-D array of {nrow} entries")
-            mp = keep.ctypes.data
-    it = np.zeros(max(nb, 1), np.int32)
-    nr = np.zeros(max(nb, 1), np.float64)
-    times = np.zeros(7, np.float64)
-    f = L.hpccg_hip_pcg_solve_device if device else L.hpccg_hip_pcg_solve
-    rc = f(M.h, nb, bp, ldb_, xp, ldx_, mp, max_iter, tolerance, it.ctypes.data_as(C.POINTER(C.c_int)),
-           nr.ctypes.data_as(C.POINTER(C.c_double)), times.ctypes.data_as(C.POINTER(C.c_double)))
-    _check(rc, "HPCCG_pcg")
-    return rc, it[:nb], nr[:nb], times
-
-
-def pcg_live_workspaces() -> int:
-    """Matrices that hold a pcg workspace (0 when the library was never loaded)."""
-    if _pcg_lib is None:
-        return 0
-    c = C.c_int(0)
-    _check(_pcg_lib.hpccg_hip_pcg_live_workspaces(C.byref(c)), "pcg_live_workspaces")
-    return c.value
-
-
-# ---------------------------------------------------------------------------
-# single-reduction preconditioned solve (include/hpccg_hip_srcg.h)
-# ---------------------------------------------------------------------------
-def HPCCG_srcg(M: Matrix, B, X, max_iter: int = 500, tolerance: float = 0.0, minv=None, device=False, nrhs=None,
-               ldb=None, ldx=None):
-    """HPCCG_pcg in the single-reduction (Chronopoulos-Gear) form
-    (hpccg_hip_srcg_solve[_device]): one finalize and three launches per
-    iteration for one more vector. Its first iteration is HPCCG_pcg's bit for
-    bit; later ones agree to rounding. B, X, minv and the return value: as
-    HPCCG_pcg. X is updated in place."""
-    L = srcg_lib()
-    B, X = _one_column(B, "B"), _one_column(X, "X")
-    bp, nb, ldb_ = _cols(B, nrhs, ldb, "B")
-    xp, nx_, ldx_ = _cols(X, nrhs, ldx, "X")
-    if nb != nx_:
-        raise HPCCGError(f"B holds {nb} columns, X {nx_}")
-    if not device and not (isinstance(B, np.ndarray) and isinstance(X, np.ndarray)):
-        raise HPCCGError("host solve: B and X are numpy arrays")
-    mp, keep = (None, None) if minv is None else _minv_ptr(M, minv, device)
-    it = np.zeros(max(nb, 1), np.int32)
-    nr = np.zeros(max(nb, 1), np.float64)
-    times = np.zeros(7, np.float64)
-    f = L.hpccg_hip_srcg_solve_device if device else L.hpccg_hip_srcg_solve
-    rc = f(M.h, nb, bp, ldb_, xp, ldx_, mp, max_iter, tolerance, it.ctypes.data_as(C.POINTER(C.c_int)),
-           nr.ctypes.data_as(C.POINTER(C.c_double)), times.ctypes.data_as(C.POINTER(C.c_double)))
-    _check(rc, "HPCCG_srcg")
-    return rc, it[:nb], nr[:nb], times
-
-
-def srcg_live_workspaces() -> int:
-    """Matrices that hold a srcg workspace (0 when the library was never loaded)."""
-    if _srcg_lib is None:
-        return 0
-    c = C.c_int(0)
-    _check(_srcg_lib.hpccg_hip_srcg_live_workspaces(C.byref(c)), "srcg_live_workspaces")
-    return c.value
-
-
-# ---------------------------------------------------------------------------
-# Chebyshev polynomial preconditioned solve (include/hpccg_hip_poly.h)
 # ---------------------------------------------------------------------------
 def _minv_ptr(M: Matrix, minv, device):
     """(pointer, keep-alive) of a caller's m: nrow entries, host or device."""
@@ -1290,16 +1000,11 @@ def _minv_ptr(M: Matrix, minv, device):
     return keep.ctypes.data, keep
 
 
-def HPCCG_poly(M: Matrix, B, X, degree: int = 2, lmin=None, lmax=None, minv=None, device=False, max_iter: int = 500,
-               tolerance: float = 0.0, nrhs=None, ldb=None, ldx=None):
-    """nrhs CG solves against M preconditioned by the Chebyshev polynomial of
-    `degree` steps in diag(minv) A on [lmin, lmax] (hpccg_hip_poly_solve[_device]);
-    minv None is Jacobi, lmax None the symmetric Gershgorin bound, lmin None
-    lmax / 30. Degree 0 is HPCCG_pcg bit for bit. A caller's bounds are not
-    verified. The loop test, niters and normr are on the 2-norm of r, as in
-    HPCCG. B, X, minv: as HPCCG_pcg. X is updated in place. Returns
-    (ierr, niters[nrhs], normr[nrhs], times)."""
-    L = poly_lib()
+def _column_solve(what, solve, M, B, X, minv, device, nrhs, ldb, ldx, *rest):
+    """What the one-rank preconditioned solves share: the columns of B and X (a
+    1-D array or tensor is one column), a caller's minv, the call of solve
+    (the library's host or device entry point; rest: its arguments between
+    minv and niters) and the result (ierr, niters[nrhs], normr[nrhs], times)."""
     B, X = _one_column(B, "B"), _one_column(X, "X")
     bp, nb, ldb_ = _cols(B, nrhs, ldb, "B")
     xp, nx_, ldx_ = _cols(X, nrhs, ldx, "X")
@@ -1311,12 +1016,67 @@ def HPCCG_poly(M: Matrix, B, X, degree: int = 2, lmin=None, lmax=None, minv=None
     it = np.zeros(max(nb, 1), np.int32)
     nr = np.zeros(max(nb, 1), np.float64)
     times = np.zeros(7, np.float64)
-    f = L.hpccg_hip_poly_solve_device if device else L.hpccg_hip_poly_solve
-    rc = f(M.h, nb, bp, ldb_, xp, ldx_, mp, int(degree), 0.0 if lmin is None else float(lmin),
-           0.0 if lmax is None else float(lmax), max_iter, tolerance, it.ctypes.data_as(C.POINTER(C.c_int)),
-           nr.ctypes.data_as(C.POINTER(C.c_double)), times.ctypes.data_as(C.POINTER(C.c_double)))
-    _check(rc, "HPCCG_poly")
+    rc = solve(M.h, nb, bp, ldb_, xp, ldx_, mp, *rest, it.ctypes.data_as(C.POINTER(C.c_int)),
+               nr.ctypes.data_as(C.POINTER(C.c_double)), times.ctypes.data_as(C.POINTER(C.c_double)))
+    _check(rc, what)
     return rc, it[:nb], nr[:nb], times
+
+
+def HPCCG_pcg(M: Matrix, B, X, max_iter: int = 500, tolerance: float = 0.0, minv=None, device=False, nrhs=None,
+              ldb=None, ldx=None):
+    """nrhs preconditioned CG solves against M with M^-1 = diag(minv)
+    (hpccg_hip_pcg_solve[_device]); minv None is Jacobi, 1 / a_ii. The loop
+    test, niters and normr are on the 2-norm of r, as in HPCCG. B, X: as
+    HPCCG_batch (a 1-D array or tensor is one column); minv: nrow entries, all
+    finite and > 0 -- numpy on the host or, with device=True, a tensor / device
+    pointer. X is updated in place. Returns (ierr, niters[nrhs], normr[nrhs],
+    times)."""
+    L = pcg_lib()
+    return _column_solve("HPCCG_pcg", L.hpccg_hip_pcg_solve_device if device else L.hpccg_hip_pcg_solve, M, B, X, minv,
+                         device, nrhs, ldb, ldx, max_iter, tolerance)
+
+
+def pcg_live_workspaces() -> int:
+    """Matrices that hold a pcg workspace (0 when the library was never loaded)."""
+    return _live("pcg", "pcg_live_workspaces")
+
+
+# ---------------------------------------------------------------------------
+# single-reduction preconditioned solve (include/hpccg_hip_srcg.h)
+# ---------------------------------------------------------------------------
+def HPCCG_srcg(M: Matrix, B, X, max_iter: int = 500, tolerance: float = 0.0, minv=None, device=False, nrhs=None,
+               ldb=None, ldx=None):
+    """HPCCG_pcg in the single-reduction (Chronopoulos-Gear) form
+    (hpccg_hip_srcg_solve[_device]): one finalize and three launches per
+    iteration for one more vector. Its first iteration is HPCCG_pcg's bit for
+    bit; later ones agree to rounding. B, X, minv and the return value: as
+    HPCCG_pcg. X is updated in place."""
+    L = srcg_lib()
+    return _column_solve("HPCCG_srcg", L.hpccg_hip_srcg_solve_device if device else L.hpccg_hip_srcg_solve, M, B, X, minv,
+                         device, nrhs, ldb, ldx, max_iter, tolerance)
+
+
+def srcg_live_workspaces() -> int:
+    """Matrices that hold a srcg workspace (0 when the library was never loaded)."""
+    return _live("srcg", "srcg_live_workspaces")
+
+
+# ---------------------------------------------------------------------------
+# Chebyshev polynomial preconditioned solve (include/hpccg_hip_poly.h)
+# ---------------------------------------------------------------------------
+def HPCCG_poly(M: Matrix, B, X, degree: int = 2, lmin=None, lmax=None, minv=None, device=False, max_iter: int = 500,
+               tolerance: float = 0.0, nrhs=None, ldb=None, ldx=None):
+    """nrhs CG solves against M preconditioned by the Chebyshev polynomial of
+    `degree` steps in diag(minv) A on [lmin, lmax] (hpccg_hip_poly_solve[_device]);
+    minv None is Jacobi, lmax None the symmetric Gershgorin bound, lmin None
+    lmax / 30. Degree 0 is HPCCG_pcg bit for bit. A caller's bounds are not
+    verified. The loop test, niters and normr are on the 2-norm of r, as in
+    HPCCG. B, X, minv: as HPCCG_pcg. X is updated in place. Returns
+    (ierr, niters[nrhs], normr[nrhs], times)."""
+    L = poly_lib()
+    return _column_solve("HPCCG_poly", L.hpccg_hip_poly_solve_device if device else L.hpccg_hip_poly_solve, M, B, X, minv,
+                         device, nrhs, ldb, ldx, int(degree), 0.0 if lmin is None else float(lmin),
+                         0.0 if lmax is None else float(lmax), max_iter, tolerance)
 
 
 def poly_bound(M: Matrix, minv=None) -> float:
@@ -1331,11 +1091,7 @@ def poly_bound(M: Matrix, minv=None) -> float:
 
 def poly_live_workspaces() -> int:
     """Matrices that hold a poly workspace (0 when the library was never loaded)."""
-    if _poly_lib is None:
-        return 0
-    c = C.c_int(0)
-    _check(_poly_lib.hpccg_hip_poly_live_workspaces(C.byref(c)), "poly_live_workspaces")
-    return c.value
+    return _live("poly", "poly_live_workspaces")
 
 
 # ---------------------------------------------------------------------------
@@ -1350,23 +1106,9 @@ def HPCCG_poly32(M: Matrix, B, X, degree: int = 2, lmin=None, lmax=None, minv=No
     bit for bit; degree 0 is HPCCG_pcg bit for bit on any matrix. A matrix
     outside fp32 range is refused. Arguments and return: HPCCG_poly's."""
     L = poly32_lib()
-    B, X = _one_column(B, "B"), _one_column(X, "X")
-    bp, nb, ldb_ = _cols(B, nrhs, ldb, "B")
-    xp, nx_, ldx_ = _cols(X, nrhs, ldx, "X")
-    if nb != nx_:
-        raise HPCCGError(f"B holds {nb} columns, X {nx_}")
-    if not device and not (isinstance(B, np.ndarray) and isinstance(X, np.ndarray)):
-        raise HPCCGError("host solve: B and X are numpy arrays")
-    mp, keep = (None, None) if minv is None else _minv_ptr(M, minv, device)
-    it = np.zeros(max(nb, 1), np.int32)
-    nr = np.zeros(max(nb, 1), np.float64)
-    times = np.zeros(7, np.float64)
-    f = L.hpccg_hip_poly32_solve_device if device else L.hpccg_hip_poly32_solve
-    rc = f(M.h, nb, bp, ldb_, xp, ldx_, mp, int(degree), 0.0 if lmin is None else float(lmin),
-           0.0 if lmax is None else float(lmax), max_iter, tolerance, it.ctypes.data_as(C.POINTER(C.c_int)),
-           nr.ctypes.data_as(C.POINTER(C.c_double)), times.ctypes.data_as(C.POINTER(C.c_double)))
-    _check(rc, "HPCCG_poly32")
-    return rc, it[:nb], nr[:nb], times
+    return _column_solve("HPCCG_poly32", L.hpccg_hip_poly32_solve_device if device else L.hpccg_hip_poly32_solve, M, B, X, minv,
+                         device, nrhs, ldb, ldx, int(degree), 0.0 if lmin is None else float(lmin),
+                         0.0 if lmax is None else float(lmax), max_iter, tolerance)
 
 
 def poly32_bound(M: Matrix, minv=None) -> float:
@@ -1390,11 +1132,7 @@ def poly32_info(M: Matrix) -> dict:
 
 def poly32_live_workspaces() -> int:
     """Matrices that hold a poly32 workspace (0 when the library was never loaded)."""
-    if _poly32_lib is None:
-        return 0
-    c = C.c_int(0)
-    _check(_poly32_lib.hpccg_hip_poly32_live_workspaces(C.byref(c)), "poly32_live_workspaces")
-    return c.value
+    return _live("poly32", "poly32_live_workspaces")
 
 
 # ---------------------------------------------------------------------------
@@ -1548,17 +1286,7 @@ def group_HPCCG_pcg(Ms: list, Bs, Xs, max_iter: int = 500, tolerance: float = 0.
     xp, nx_, ldx_ = _group_cols(Xs, nrhs, ldx, "Xs")
     if nb != nx_:
         raise HPCCGError(f"Bs holds {nb} columns, Xs {nx_}")
-    mp = None
-    if minvs is not None:
-        if len(minvs) != P:
-            raise HPCCGError(f"{P} members, {len(minvs)} minv vectors")
-        ptrs = []
-        for r, (M, m) in enumerate(zip(Ms, minvs)):
-            nrow = int(M.info()["nrow"])
-            if not isinstance(m, int) and (m.dim() != 1 or m.shape[0] < nrow or (m.shape[0] > 1 and m.stride(0) != 1)):
-                raise HPCCGError(f"minvs[{r}]: a contiguous 1-D tensor of {nrow} entries")
-            ptrs.append(_ptr(m))
-        mp = (C.c_void_p * P)(*ptrs)
+    mp = _group_minvs(Ms, minvs)
     it = np.zeros(max(nb, 1), np.int32)
     nr = np.zeros(max(nb, 1), np.float64)
     times = np.zeros(7, np.float64)
@@ -1605,26 +1333,17 @@ def group_last_trace_pcg(Ms: list, col: int, cap: int = 100000) -> np.ndarray:
 
 def group_pcg_workspace_bytes(M: Matrix) -> int:
     """Device bytes member M's group pcg workspace holds (0: none)."""
-    if _pcg_group_lib is None:
-        return 0
-    v = C.c_longlong(0)
-    _check(_pcg_group_lib.hpccg_hip_group_pcg_workspace_bytes(M.h, C.byref(v)), "group_pcg_workspace_bytes")
-    return v.value
+    return _workspace_bytes("pcg_group", "group_pcg_workspace_bytes", M.h)
 
 
 def group_pcg_release(M: Matrix) -> None:
     """Free member M's group pcg workspace (with its cached 1 / a_ii) now (close() does it too)."""
-    if M.h and _pcg_group_lib is not None:
-        _check(_pcg_group_lib.hpccg_hip_group_pcg_release(M.h), "group_pcg_release")
+    _release("pcg_group", "group_pcg_release", M.h)
 
 
 def group_pcg_live_workspaces() -> int:
     """Matrices that hold a group pcg workspace (0 when the library was never loaded)."""
-    if _pcg_group_lib is None:
-        return 0
-    c = C.c_int(0)
-    _check(_pcg_group_lib.hpccg_hip_group_pcg_live_workspaces(C.byref(c)), "group_pcg_live_workspaces")
-    return c.value
+    return _live("pcg_group", "group_pcg_live_workspaces")
 
 
 # ---------------------------------------------------------------------------
@@ -1738,26 +1457,17 @@ def group_last_spectrum_poly(Ms: list) -> tuple:
 
 def group_poly_workspace_bytes(M: Matrix) -> int:
     """Device bytes member M's group poly workspace holds (0: none)."""
-    if _poly_group_lib is None:
-        return 0
-    v = C.c_longlong(0)
-    _check(_poly_group_lib.hpccg_hip_group_poly_workspace_bytes(M.h, C.byref(v)), "group_poly_workspace_bytes")
-    return v.value
+    return _workspace_bytes("poly_group", "group_poly_workspace_bytes", M.h)
 
 
 def group_poly_release(M: Matrix) -> None:
     """Free member M's group poly workspace (with its caches) now (close() does it too)."""
-    if M.h and _poly_group_lib is not None:
-        _check(_poly_group_lib.hpccg_hip_group_poly_release(M.h), "group_poly_release")
+    _release("poly_group", "group_poly_release", M.h)
 
 
 def group_poly_live_workspaces() -> int:
     """Matrices that hold a group poly workspace (0 when the library was never loaded)."""
-    if _poly_group_lib is None:
-        return 0
-    c = C.c_int(0)
-    _check(_poly_group_lib.hpccg_hip_group_poly_live_workspaces(C.byref(c)), "group_poly_live_workspaces")
-    return c.value
+    return _live("poly_group", "group_poly_live_workspaces")
 
 
 # ---------------------------------------------------------------------------
@@ -1846,26 +1556,17 @@ def group_last_spectrum_poly32(Ms: list) -> tuple:
 
 def group_poly32_workspace_bytes(M: Matrix) -> int:
     """Device bytes member M's group poly32 workspace holds, its fp32 image included (0: none)."""
-    if _poly32_group_lib is None:
-        return 0
-    v = C.c_longlong(0)
-    _check(_poly32_group_lib.hpccg_hip_group_poly32_workspace_bytes(M.h, C.byref(v)), "group_poly32_workspace_bytes")
-    return v.value
+    return _workspace_bytes("poly32_group", "group_poly32_workspace_bytes", M.h)
 
 
 def group_poly32_release(M: Matrix) -> None:
     """Free member M's group poly32 workspace (with its caches and its fp32 image) now (close() does it too)."""
-    if M.h and _poly32_group_lib is not None:
-        _check(_poly32_group_lib.hpccg_hip_group_poly32_release(M.h), "group_poly32_release")
+    _release("poly32_group", "group_poly32_release", M.h)
 
 
 def group_poly32_live_workspaces() -> int:
     """Matrices that hold a group poly32 workspace (0 when the library was never loaded)."""
-    if _poly32_group_lib is None:
-        return 0
-    c = C.c_int(0)
-    _check(_poly32_group_lib.hpccg_hip_group_poly32_live_workspaces(C.byref(c)), "group_poly32_live_workspaces")
-    return c.value
+    return _live("poly32_group", "group_poly32_live_workspaces")
 
 
 def HPC_sparsemv(M: Matrix, x, y) -> int:

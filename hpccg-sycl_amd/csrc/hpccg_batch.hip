@@ -24,7 +24,9 @@
 // The recurrence itself -- the column's state, the bodies of the p update, the
 // SpMM epilogue, the update and the finalize, the workspace registry, the
 // launch loop and its read-back -- is hpccg_columns.h, the fp64 SpMM loops are
-// hpccg_spmm.h; this unit adds its args, its launch dispatch and a guarded r.
+// hpccg_spmm.h; the matrix check and the bodies of the bookkeeping exports are
+// hpccg_onerank_host.h; this unit adds its args, its launch dispatch (two and
+// four columns only: one is forwarded to the main library) and a guarded r.
 //
 // Over an in-process rank group (include/hpccg_hip_batch_group.h; the last part
 // of the host code): every member runs these kernels on its rows, the ghost
@@ -46,7 +48,7 @@
 #include "../../include/hpccg_hip_batch.h"
 #include "../../include/hpccg_hip_batch_group.h"
 #include "hpccg_group.h"
-#include "hpccg_spmm.h"
+#include "hpccg_onerank_host.h"
 
 #pragma clang fp contract(off)
 
@@ -128,6 +130,7 @@ struct Workspace : TraceWorkspace, GroupMember {
         rbuf = x = b = nullptr;
     }
     void free_own_rest() { destroy_events(); }
+    long long total_bytes() const { return bytes; }
 };
 
 // The matrix's workspace record with room for nrhs columns (ncols 0: the record
@@ -152,17 +155,12 @@ int get_workspace(hpccg_hip_matrix* M, const MatrixView& v, int ncols, int max_i
     return 0;
 }
 
-// What the batch runs on: one rank, no halo (group1: also the one member of a
-// one-rank in-process group, which is that).
-int check_matrix(hpccg_hip_matrix* M, MatrixView* v, bool group1 = false)
-{
-    TRY(hpccg_hip_internal_view(M, v));
-    if (v->in_group && !(group1 && v->nranks == 1)) return fail(HPCCG_HIP_EINVAL, "batch: the matrix is a member of an in-process group (one rank only)");
-    if (v->nranks > 1) return fail(HPCCG_HIP_EINVAL, "batch: the matrix belongs to a communicator of %d ranks (one rank only)", v->nranks);
-    if (v->ghost_lo || v->ghost_hi) return fail(HPCCG_HIP_EINVAL, "batch: the matrix has halo rows (one rank only)");
-    if (!v->has_a && !v->has_sell) return fail(HPCCG_HIP_EINVAL, "batch: the matrix holds no device image");
-    return 0;
-}
+// What hpccg_onerank_host.h's matrix check and bookkeeping bodies go by.
+struct Batch {
+    using Workspace = hpccg::Workspace;
+    static constexpr const char* who = "batch";
+    static constexpr const char* solve_name = "batch";
+};
 
 BatchArgs make_args(const Workspace* w, int nrhs)
 {
@@ -270,7 +268,7 @@ int solve_common(hpccg_hip_matrix* M, int nrhs, const double* B, long long ldb, 
 {
     TRY(check_solve_args(M, nrhs, B, ldb, X, ldx, max_iter, niters, normr));
     MatrixView v;
-    TRY(check_matrix(M, &v, group1));
+    TRY(check_matrix(Batch::who, M, &v, group1));
     if (ldb < v.n || ldx < v.n)
         return fail(HPCCG_HIP_EINVAL, "batch: leading dimensions %lld, %lld below the %d rows", ldb, ldx, v.n);
     if (times) std::fill(times, times + 7, 0.0);
@@ -324,7 +322,7 @@ int sparsemv_one(hpccg_hip_matrix* M, int nrhs, const double* X_dev, long long l
     if (!M || !X_dev || !Y_dev) return fail(HPCCG_HIP_EINVAL, "batch: NULL argument");
     if (nrhs <= 0) return fail(HPCCG_HIP_EINVAL, "batch: nrhs %d (at least 1)", nrhs);
     MatrixView v;
-    TRY(check_matrix(M, &v, group1));
+    TRY(check_matrix(Batch::who, M, &v, group1));
     if (ldx < v.n || ldy < v.n)
         return fail(HPCCG_HIP_EINVAL, "batch: leading dimensions %lld, %lld below the %d rows", ldx, ldy, v.n);
     if (v.n == 0) return 0;
@@ -456,13 +454,7 @@ int hpccg_hip_batch_solve(hpccg_hip_matrix* M, int nrhs, const double* B, long l
 
 int hpccg_hip_batch_last_trace(const hpccg_hip_matrix* M, int col, double* out, int cap)
 {
-    if (!M || !out) return fail(HPCCG_HIP_EINVAL, "batch: NULL argument");
-    const Workspace* w = g_ws<Workspace>.find(M);
-    const int n = copy_trace(w, col, out, cap);
-    if (n < 0)
-        return fail(HPCCG_HIP_EINVAL, "batch: no trace of column %d (the last batch solve had %d)", col,
-                    w ? (int)w->trace.size() : 0);
-    return n;
+    return unit_last_trace<Batch>(M, col, out, cap);
 }
 
 int hpccg_hip_batch_sparsemv(hpccg_hip_matrix* M, int nrhs, const double* X_dev, long long ldx, double* Y_dev,
@@ -471,27 +463,14 @@ int hpccg_hip_batch_sparsemv(hpccg_hip_matrix* M, int nrhs, const double* X_dev,
     return sparsemv_one(M, nrhs, X_dev, ldx, Y_dev, ldy, false);
 }
 
-int hpccg_hip_batch_release(hpccg_hip_matrix* M)
-{
-    if (!M) return fail(HPCCG_HIP_EINVAL, "batch: NULL argument");
-    g_ws<Workspace>.drop(M);
-    return 0;
-}
+int hpccg_hip_batch_release(hpccg_hip_matrix* M) { return unit_release<Batch>(M); }
 
 int hpccg_hip_batch_workspace_bytes(const hpccg_hip_matrix* M, long long* bytes)
 {
-    if (!M || !bytes) return fail(HPCCG_HIP_EINVAL, "batch: NULL argument");
-    const Workspace* w = g_ws<Workspace>.find(M);
-    *bytes = w ? w->bytes : 0;
-    return 0;
+    return unit_workspace_bytes<Batch>(M, bytes);
 }
 
-int hpccg_hip_batch_live_workspaces(int* count)
-{
-    if (!count) return fail(HPCCG_HIP_EINVAL, "batch: NULL argument");
-    *count = g_ws<Workspace>.live();
-    return 0;
-}
+int hpccg_hip_batch_live_workspaces(int* count) { return unit_live_workspaces<Batch>(count); }
 
 // ---- include/hpccg_hip_batch_group.h ---------------------------------------
 int hpccg_hip_group_batch_abi_version(void) { return 1; }

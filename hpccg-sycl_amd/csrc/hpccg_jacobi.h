@@ -1,8 +1,8 @@
 // hpccg_jacobi.h -- the diagonal preconditioner's vector, shared by the
-// preconditioned units (hpccg_pcg.hip, hpccg_pcg_group.hip, and through
-// hpccg_poly_host.h hpccg_poly.hip, hpccg_poly32.hip, hpccg_poly_group.hip):
-// reading a_ii from the matrix image, checking a caller's m, and the part of a workspace that
-// holds them while its columns grow.
+// preconditioned units (through hpccg_onerank_host.h hpccg_pcg.hip,
+// hpccg_srcg.hip, hpccg_pcg_group.hip and the four polynomial units): reading
+// a_ii from the matrix image, checking a caller's m, and the part of a
+// workspace that holds them while its columns grow.
 //   device  the bodies of the diagonal kernel and of the check kernel; a unit's
 //           __global__ entry points are thin wrappers over them
 //   host    DiagArgs from a matrix view; JacobiCache (a unit's Workspace derives
@@ -98,7 +98,8 @@ __device__ __forceinline__ void check_body(const double* __restrict__ m, int n, 
 typedef void (*DiagKernel)(DiagArgs, double*, double*, int*);
 typedef void (*CheckKernel)(const double*, int, int*);
 
-DiagArgs diag_args(const MatrixView& v)
+// (inline: hpccg_onerank_host.h brings this header to units without a preconditioner)
+inline DiagArgs diag_args(const MatrixView& v)
 {
     DiagArgs d{};
     d.n = v.n;

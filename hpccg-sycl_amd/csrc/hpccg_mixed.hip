@@ -30,9 +30,11 @@
 // The recurrence itself -- the column's state, those bodies, the workspace
 // registry and the launch loop -- is hpccg_columns.h; the image -- its convert
 // body, its slot loops, its record and builder on the host -- is
-// hpccg_spmm32.h, shared with hpccg_poly32.hip. This unit adds the frames of
-// its two SpMM kernels and the refinement. Every dot keeps the rounding shape
-// of hpccg_device.h. No kernel here waits on another block.
+// hpccg_spmm32.h, shared with hpccg_poly32.hip; the matrix check and the bodies
+// of the release, workspace_bytes and live_workspaces exports are
+// hpccg_onerank_host.h. This unit adds the frames of its two SpMM kernels and
+// the refinement. Every dot keeps the rounding shape of hpccg_device.h. No
+// kernel here waits on another block.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -42,7 +44,7 @@
 #include <vector>
 
 #include "../../include/hpccg_hip_mixed.h"
-#include "hpccg_columns.h"
+#include "hpccg_onerank_host.h"
 #include "hpccg_spmm32.h"
 
 #pragma clang fp contract(off)
@@ -229,6 +231,7 @@ struct Workspace : ColWorkspace, Image32 {
         refine = false;
     }
     void free_own_rest() { free_image(); }
+    long long total_bytes() const { return bytes + img_bytes; }
 };
 
 // The fp32 image, built once per matrix (hpccg_spmm32.h).
@@ -255,16 +258,11 @@ int ensure_vectors(Workspace* w, int ncols, int max_iter, bool refine)
     });
 }
 
-// What the mixed library runs on: one rank, no halo.
-int check_matrix(hpccg_hip_matrix* M, MatrixView* v)
-{
-    TRY(hpccg_hip_internal_view(M, v));
-    if (v->in_group) return fail(HPCCG_HIP_EINVAL, "mixed: the matrix is a member of an in-process group (one rank only)");
-    if (v->nranks > 1) return fail(HPCCG_HIP_EINVAL, "mixed: the matrix belongs to a communicator of %d ranks (one rank only)", v->nranks);
-    if (v->ghost_lo || v->ghost_hi) return fail(HPCCG_HIP_EINVAL, "mixed: the matrix has halo rows (one rank only)");
-    if (!v->has_a && !v->has_sell) return fail(HPCCG_HIP_EINVAL, "mixed: the matrix holds no device image");
-    return 0;
-}
+// What hpccg_onerank_host.h's matrix check and bookkeeping bodies go by.
+struct Mixed {
+    using Workspace = hpccg::Workspace;
+    static constexpr const char* who = "mixed";
+};
 
 // inner: the recurrence runs on the refinement's (r_s, d) instead of (b, x)
 MixedArgs make_args(const Workspace* w, int nrhs, bool inner)
@@ -465,7 +463,7 @@ int solve_common(hpccg_hip_matrix* M, int nrhs, const double* B, long long ldb, 
         return fail(HPCCG_HIP_EINVAL, "mixed: inner_rtol %g (in [0, 1); negative: the default)", inner_rtol);
     if (inner_rtol < 0.0) inner_rtol = kInnerRtolDefault;
     MatrixView v;
-    TRY(check_matrix(M, &v));
+    TRY(check_matrix(Mixed::who, M, &v));
     if (ldb < v.n || ldx < v.n)
         return fail(HPCCG_HIP_EINVAL, "mixed: leading dimensions %lld, %lld below the %d rows", ldb, ldx, v.n);
     if (times) std::fill(times, times + 7, 0.0);
@@ -549,7 +547,7 @@ int hpccg_hip_mixed_sparsemv(hpccg_hip_matrix* M, int nrhs, const double* X_dev,
     if (!M || !X_dev || !Y_dev) return fail(HPCCG_HIP_EINVAL, "mixed: NULL argument");
     if (nrhs <= 0) return fail(HPCCG_HIP_EINVAL, "mixed: nrhs %d (at least 1)", nrhs);
     MatrixView v;
-    TRY(check_matrix(M, &v));
+    TRY(check_matrix(Mixed::who, M, &v));
     if (ldx < v.n || ldy < v.n)
         return fail(HPCCG_HIP_EINVAL, "mixed: leading dimensions %lld, %lld below the %d rows", ldx, ldy, v.n);
     if (v.n == 0) return 0;
@@ -574,7 +572,7 @@ int hpccg_hip_mixed_info(hpccg_hip_matrix* M, long long out[4])
 {
     if (!M || !out) return fail(HPCCG_HIP_EINVAL, "mixed: NULL argument");
     MatrixView v;
-    TRY(check_matrix(M, &v));
+    TRY(check_matrix(Mixed::who, M, &v));
     out[0] = 1;
     out[1] = out[2] = out[3] = 0;
     if (v.n == 0) return 0;
@@ -611,26 +609,13 @@ int hpccg_hip_mixed_last_sweeps(const hpccg_hip_matrix* M, int col, int* iters, 
     return (int)r->iters.size();
 }
 
-int hpccg_hip_mixed_release(hpccg_hip_matrix* M)
-{
-    if (!M) return fail(HPCCG_HIP_EINVAL, "mixed: NULL argument");
-    g_ws<Workspace>.drop(M);
-    return 0;
-}
+int hpccg_hip_mixed_release(hpccg_hip_matrix* M) { return unit_release<Mixed>(M); }
 
 int hpccg_hip_mixed_workspace_bytes(const hpccg_hip_matrix* M, long long* bytes)
 {
-    if (!M || !bytes) return fail(HPCCG_HIP_EINVAL, "mixed: NULL argument");
-    const Workspace* w = g_ws<Workspace>.find(M);
-    *bytes = w ? w->bytes + w->img_bytes : 0;
-    return 0;
+    return unit_workspace_bytes<Mixed>(M, bytes);
 }
 
-int hpccg_hip_mixed_live_workspaces(int* count)
-{
-    if (!count) return fail(HPCCG_HIP_EINVAL, "mixed: NULL argument");
-    *count = g_ws<Workspace>.live();
-    return 0;
-}
+int hpccg_hip_mixed_live_workspaces(int* count) { return unit_live_workspaces<Mixed>(count); }
 
 }  // extern "C"

@@ -22,21 +22,20 @@
 //             holds a_ii of each of its rows
 // The group engine -- the group and its checks, the guarded p column, the
 // bodies of the sum and halo kernels, the halo, the sum, the launch loop and
-// the staging of B and X -- is hpccg_group.h, shared with hpccg_batch.hip; this
-// unit adds its args, its launch dispatch and the members' preconditioner.
+// the staging of B and X -- is hpccg_group.h, shared with hpccg_batch.hip; the
+// dispatch of a launch on a chunk's columns and SpMM form and the bookkeeping
+// exports are hpccg_onerank_host.h, shared with hpccg_pcg.hip; this unit adds
+// its args, its sum and halo launchers and the members' preconditioner.
 // Ordering between the members is by stream events (group_halo and group_sum
 // there). No kernel here waits on another block.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
 #include <cstdlib>
-#include <vector>
 
 #include "../../include/hpccg_hip_pcg_group.h"
 #include "hpccg_group.h"
-#include "hpccg_jacobi.h"
-#include "hpccg_spmm.h"
+#include "hpccg_onerank_host.h"
 
 #pragma clang fp contract(off)
 
@@ -141,6 +140,7 @@ struct Workspace : TraceWorkspace, GroupMember, JacobiCache {
         free_cache();
         destroy_events();
     }
+    long long total_bytes() const { return bytes + rest_bytes; }
 };
 
 // The member's cache (hpccg_jacobi.h) and its two events.
@@ -208,65 +208,30 @@ PcgArgs make_args(const Workspace* w, int nrhs, const double* m)
     return a;
 }
 
-#define HPCCG_PCG_R(KERNEL, ...)                                                           \
-    do {                                                                                   \
-        if (R == 4)                                                                        \
-            hipLaunchKernelGGL((KERNEL<__VA_ARGS__ 4>), g, b, 0, s, a, prologue);          \
-        else if (R == 2)                                                                   \
-            hipLaunchKernelGGL((KERNEL<__VA_ARGS__ 2>), g, b, 0, s, a, prologue);          \
-        else                                                                               \
-            hipLaunchKernelGGL((KERNEL<__VA_ARGS__ 1>), g, b, 0, s, a, prologue);          \
-    } while (0)
+// hpccg_onerank_host.h's launchers over this unit's kernels
+struct PcgGroupUnit {
+    using Args = PcgArgs;
+    using Workspace = hpccg::Workspace;
+    static constexpr const char* who = "group pcg";
 
-void launch_spmm(const Workspace* w, PcgArgs a, bool prologue)
-{
-    const dim3 g(a.grid), b(kBlock);
-    hipStream_t s = w->v.stream;
-    for_chunks(a.nrhs, true, [&](int c0, int R) {
-        a.c0 = c0;
-        if (!w->v.has_a)
-            HPCCG_PCG_R(k_pcg_group_spmm_sell, );
-        else if (a.a_width == 27 && R == 4 && a.nt)
-            hipLaunchKernelGGL((k_pcg_group_spmm_a<27, 4, 5>), g, b, 0, s, a, prologue);
-        else if (a.a_width == 27)
-            HPCCG_PCG_R(k_pcg_group_spmm_a, 27, );
-        else if (a.a_width == 7)
-            HPCCG_PCG_R(k_pcg_group_spmm_a, 7, );
-        else
-            HPCCG_PCG_R(k_pcg_group_spmm_a, 0, );
-    });
-}
+    static constexpr auto init = k_pcg_group_init;
+    template <int kW, int kR, int kWaves>
+    static constexpr auto spmm_a = k_pcg_group_spmm_a<kW, kR, kWaves>;
+    template <int kR>
+    static constexpr auto spmm_sell = k_pcg_group_spmm_sell<kR>;
+    // (store_total: always 1 here, a member's part; the state is the group sum's)
+    static constexpr auto finalize = k_pcg_group_finalize;
+};
+constexpr const char* kGroupWho = PcgGroupUnit::who;
 
 void launch_p(const Workspace* w, PcgArgs a, bool prologue)
 {
-    const dim3 g(a.grid), b(kBlock);
-    hipStream_t s = w->v.stream;
-    for_chunks(a.nrhs, true, [&](int c0, int R) {
-        a.c0 = c0;
-        HPCCG_PCG_R(k_pcg_group_p, );
-    });
+    launch_chunks(w, a, prologue, [](auto r) { return k_pcg_group_p<decltype(r)::value>; });
 }
 
 void launch_update(const Workspace* w, PcgArgs a, bool prologue)
 {
-    const dim3 g(a.grid), b(kBlock);
-    hipStream_t s = w->v.stream;
-    for_chunks(a.nrhs, true, [&](int c0, int R) {
-        a.c0 = c0;
-        HPCCG_PCG_R(k_pcg_group_update, );
-    });
-}
-#undef HPCCG_PCG_R
-
-// (store_total: always 1 here, a member's part; the state is the group sum's)
-void launch_finalize(const Workspace* w, const PcgArgs& a, int which, int store_total)
-{
-    hipLaunchKernelGGL(k_pcg_group_finalize, dim3(a.nrhs), dim3(kFinThreads), 0, w->v.stream, a, which, store_total);
-}
-
-void launch_init(const Workspace* w, const PcgArgs& a, int max_iter, double tol)
-{
-    hipLaunchKernelGGL(k_pcg_group_init, dim3((a.nrhs + 63) / 64), dim3(64), 0, w->v.stream, a, max_iter, tol);
+    launch_chunks(w, a, prologue, [](auto r) { return k_pcg_group_update<decltype(r)::value>; });
 }
 
 void launch_group_sum(const Workspace* w, const PcgArgs& a, const GroupTotals& gt, int which)
@@ -280,7 +245,6 @@ void launch_halo(hipStream_t s, dim3 grid, const HaloArgs& h)
 }
 
 using PcgGroup = Group<Workspace, PcgArgs>;
-constexpr const char* kGroupWho = "group pcg";
 // a group of one is checked and run like any other: nothing forwards it
 constexpr bool kOneForwarded = false;
 
@@ -309,8 +273,13 @@ int group_solve(hpccg_hip_matrix* const* Ms, const PcgGroup& G0, int nrhs, const
         G.a[r] = make_args(w, nrhs, minv ? w->muser : w->jac);
     }
     TRY(group_stage_in(G, nrhs, B, ldb, X, ldx));
-    const GroupLaunch<Workspace, PcgArgs> launch = {launch_init,     launch_p,         launch_spmm, launch_update,
-                                                    launch_finalize, launch_group_sum, copies ? nullptr : launch_halo};
+    const GroupLaunch<Workspace, PcgArgs> launch = {launch_init<PcgGroupUnit>,
+                                                    launch_p,
+                                                    launch_spmm64<PcgGroupUnit>,
+                                                    launch_update,
+                                                    launch_finalize<PcgGroupUnit>,
+                                                    launch_group_sum,
+                                                    copies ? nullptr : launch_halo};
     double wall = 0.0;
     TRY(group_run_cg(G, nrhs, max_iter, tol, launch, niters, normr, &wall));
     TRY(group_stage_out(G, nrhs, X, ldx));
@@ -392,26 +361,13 @@ int hpccg_hip_group_pcg_last_trace(hpccg_hip_matrix* const* Ms, int nranks, int 
     return n;
 }
 
-int hpccg_hip_group_pcg_release(hpccg_hip_matrix* M)
-{
-    if (!M) return fail(HPCCG_HIP_EINVAL, "group pcg: NULL argument");
-    g_ws<Workspace>.drop(M);
-    return 0;
-}
+int hpccg_hip_group_pcg_release(hpccg_hip_matrix* M) { return unit_release<PcgGroupUnit>(M); }
 
 int hpccg_hip_group_pcg_workspace_bytes(const hpccg_hip_matrix* M, long long* bytes)
 {
-    if (!M || !bytes) return fail(HPCCG_HIP_EINVAL, "group pcg: NULL argument");
-    const Workspace* w = g_ws<Workspace>.find(M);
-    *bytes = w ? w->bytes + w->rest_bytes : 0;
-    return 0;
+    return unit_workspace_bytes<PcgGroupUnit>(M, bytes);
 }
 
-int hpccg_hip_group_pcg_live_workspaces(int* count)
-{
-    if (!count) return fail(HPCCG_HIP_EINVAL, "group pcg: NULL argument");
-    *count = g_ws<Workspace>.live();
-    return 0;
-}
+int hpccg_hip_group_pcg_live_workspaces(int* count) { return unit_live_workspaces<PcgGroupUnit>(count); }
 
 }  // extern "C"

@@ -34,8 +34,10 @@
 // steps' ends, the bound's bodies -- is hpccg_poly_bodies.h, shared with the
 // unit over an in-process rank group (hpccg_poly_group.hip); the __global__
 // entry points here are wrappers over it. The host code -- the workspace, the
-// launchers, the bound, the interval, the solve -- is hpccg_poly_host.h, shared
-// with that unit and with hpccg_poly32.hip; this unit hands it its kernels.
+// launchers, the bound, the interval -- is hpccg_poly_host.h, shared with that
+// unit and with hpccg_poly32.hip, over hpccg_onerank_host.h (the dispatch, the
+// checks, the preconditioner, the solve, the bookkeeping exports), shared with
+// hpccg_pcg.hip and hpccg_srcg.hip; this unit hands them its kernels.
 #include <hip/hip_runtime.h>
 
 #include "../../include/hpccg_hip_poly.h"
@@ -209,16 +211,16 @@ int hpccg_hip_poly_last_spectrum(const hpccg_hip_matrix* M, double* lmin, double
 
 int hpccg_hip_poly_last_trace(const hpccg_hip_matrix* M, int col, double* out, int cap)
 {
-    return poly_last_trace<Poly>(M, col, out, cap);
+    return unit_last_trace<Poly>(M, col, out, cap);
 }
 
-int hpccg_hip_poly_release(hpccg_hip_matrix* M) { return poly_release<Poly>(M); }
+int hpccg_hip_poly_release(hpccg_hip_matrix* M) { return unit_release<Poly>(M); }
 
 int hpccg_hip_poly_workspace_bytes(const hpccg_hip_matrix* M, long long* bytes)
 {
-    return poly_workspace_bytes<Poly>(M, bytes);
+    return unit_workspace_bytes<Poly>(M, bytes);
 }
 
-int hpccg_hip_poly_live_workspaces(int* count) { return poly_live_workspaces<Poly>(count); }
+int hpccg_hip_poly_live_workspaces(int* count) { return unit_live_workspaces<Poly>(count); }
 
 }  // extern "C"

@@ -32,10 +32,10 @@
 // as the fp64 forms do (hpccg_spmm32.h: the same bits, a third of the x loads).
 // z alternates between two buffers as in hpccg_poly.hip; per iteration and
 // chunk of columns 5 + d launches. No kernel here waits on another block.
-// The host code is hpccg_poly_host.h, shared with hpccg_poly.hip and
-// hpccg_poly_group.hip; what this unit adds is the image (hpccg_spmm32.h's
-// Image32, built before the preconditioner) and the choice of the SpMM and
-// step forms.
+// The host code is hpccg_poly_host.h over hpccg_onerank_host.h, shared with
+// hpccg_poly.hip (the latter also with hpccg_pcg.hip and hpccg_srcg.hip); what
+// this unit adds is the image (hpccg_spmm32.h's Image32, built before the
+// preconditioner) and the choice of the SpMM and step forms.
 #include <hip/hip_runtime.h>
 
 #include "../../include/hpccg_hip_poly32.h"
@@ -317,7 +317,7 @@ int hpccg_hip_poly32_last_spectrum(const hpccg_hip_matrix* M, double* lmin, doub
 
 int hpccg_hip_poly32_last_trace(const hpccg_hip_matrix* M, int col, double* out, int cap)
 {
-    return poly_last_trace<Poly32>(M, col, out, cap);
+    return unit_last_trace<Poly32>(M, col, out, cap);
 }
 
 int hpccg_hip_poly32_info(hpccg_hip_matrix* M, long long out[4])
@@ -339,13 +339,13 @@ int hpccg_hip_poly32_info(hpccg_hip_matrix* M, long long out[4])
     });
 }
 
-int hpccg_hip_poly32_release(hpccg_hip_matrix* M) { return poly_release<Poly32>(M); }
+int hpccg_hip_poly32_release(hpccg_hip_matrix* M) { return unit_release<Poly32>(M); }
 
 int hpccg_hip_poly32_workspace_bytes(const hpccg_hip_matrix* M, long long* bytes)
 {
-    return poly_workspace_bytes<Poly32>(M, bytes);
+    return unit_workspace_bytes<Poly32>(M, bytes);
 }
 
-int hpccg_hip_poly32_live_workspaces(int* count) { return poly_live_workspaces<Poly32>(count); }
+int hpccg_hip_poly32_live_workspaces(int* count) { return unit_live_workspaces<Poly32>(count); }
 
 }  // extern "C"

@@ -36,7 +36,8 @@
 // pcg's on an inexact image.
 //
 // The host code is hpccg_poly_group_host.h (shared with hpccg_poly_group.hip)
-// over hpccg_group.h and hpccg_poly_host.h; what this unit adds is every
+// over hpccg_group.h, hpccg_poly_host.h and hpccg_onerank_host.h (the launch
+// dispatch and the bookkeeping exports); what this unit adds is every
 // member's image, built before its preconditioner, and the choice of the SpMM
 // and step forms. Ordering between the members is by stream events only. No
 // kernel here waits on another block.
@@ -366,13 +367,13 @@ int hpccg_hip_group_poly32_info(hpccg_hip_matrix* const* Ms, int nranks, long lo
     });
 }
 
-int hpccg_hip_group_poly32_release(hpccg_hip_matrix* M) { return group_poly_release<GroupPoly32>(M); }
+int hpccg_hip_group_poly32_release(hpccg_hip_matrix* M) { return unit_release<GroupPoly32>(M); }
 
 int hpccg_hip_group_poly32_workspace_bytes(const hpccg_hip_matrix* M, long long* bytes)
 {
-    return group_poly_workspace_bytes<GroupPoly32>(M, bytes);
+    return unit_workspace_bytes<GroupPoly32>(M, bytes);
 }
 
-int hpccg_hip_group_poly32_live_workspaces(int* count) { return group_poly_live_workspaces<GroupPoly32>(count); }
+int hpccg_hip_group_poly32_live_workspaces(int* count) { return unit_live_workspaces<GroupPoly32>(count); }
 
 }  // extern "C"

@@ -31,7 +31,9 @@
 // The group engine is hpccg_group.h, shared with hpccg_batch.hip and
 // hpccg_pcg_group.hip; the polynomial's workspace, arguments, launchers and
 // interval are hpccg_poly_host.h, shared with hpccg_poly.hip and
-// hpccg_poly32.hip; the members' preconditioner and bound, the update phase
+// hpccg_poly32.hip; the dispatch of a launch on a chunk's columns and SpMM form
+// and the bookkeeping exports are hpccg_onerank_host.h, shared with
+// hpccg_pcg.hip and the rest; the members' preconditioner and bound, the update phase
 // with the halos of z (group_poly_update: the ordering argument is written
 // there) and the solve are hpccg_poly_group_host.h, shared with
 // hpccg_poly32_group.hip. This unit keeps its kernels and its traits. Ordering
@@ -233,13 +235,13 @@ int hpccg_hip_group_poly_last_trace(hpccg_hip_matrix* const* Ms, int nranks, int
     return group_poly_last_trace<GroupPoly>(Ms, nranks, col, out, cap);
 }
 
-int hpccg_hip_group_poly_release(hpccg_hip_matrix* M) { return group_poly_release<GroupPoly>(M); }
+int hpccg_hip_group_poly_release(hpccg_hip_matrix* M) { return unit_release<GroupPoly>(M); }
 
 int hpccg_hip_group_poly_workspace_bytes(const hpccg_hip_matrix* M, long long* bytes)
 {
-    return group_poly_workspace_bytes<GroupPoly>(M, bytes);
+    return unit_workspace_bytes<GroupPoly>(M, bytes);
 }
 
-int hpccg_hip_group_poly_live_workspaces(int* count) { return group_poly_live_workspaces<GroupPoly>(count); }
+int hpccg_hip_group_poly_live_workspaces(int* count) { return unit_live_workspaces<GroupPoly>(count); }
 
 }  // extern "C"

@@ -3,10 +3,13 @@
 // group units (hpccg_poly_group.hip, hpccg_poly32_group.hip): the members'
 // preconditioner and bound, the group's update phase with the halos of z
 // (group_poly_update: the ordering argument is written there), the solve and
-// the bodies of the units' extern "C" functions. It stands on hpccg_group.h
-// (the group engine) and hpccg_poly_host.h (the polynomial's workspace,
-// arguments, launchers and interval).
-// A unit hands over one traits struct U: what hpccg_poly_host.h's launchers
+// the bodies of the units' extern "C" functions that take the group (release,
+// workspace_bytes and live_workspaces are hpccg_onerank_host.h's). It stands on
+// hpccg_group.h (the group engine), hpccg_poly_host.h (the polynomial's
+// workspace, arguments, launchers and interval) and, through it,
+// hpccg_onerank_host.h (the launch dispatch, the init, SpMM and finalize
+// launchers).
+// A unit hands over one traits struct U: what those two headers' launchers
 // need (Args, Workspace, row0, init, p, update, finalize, spmm_a, spmm_sell,
 // and step, step_sell where it runs the fp64 steps) and further
 //   who                   the name in front of its messages ("group poly")
@@ -371,31 +374,6 @@ int group_poly_last_trace(hpccg_hip_matrix* const* Ms, int nranks, int col, doub
         return fail(HPCCG_HIP_EINVAL, "%s: no trace of column %d (the last group solve had %d)", who, col,
                     w ? (int)w->trace.size() : 0);
     return n;
-}
-
-template <class U>
-int group_poly_release(hpccg_hip_matrix* M)
-{
-    if (!M) return fail(HPCCG_HIP_EINVAL, "%s: NULL argument", U::who);
-    g_ws<typename U::Workspace>.drop(M);
-    return 0;
-}
-
-template <class U>
-int group_poly_workspace_bytes(const hpccg_hip_matrix* M, long long* bytes)
-{
-    if (!M || !bytes) return fail(HPCCG_HIP_EINVAL, "%s: NULL argument", U::who);
-    const typename U::Workspace* w = g_ws<typename U::Workspace>.find(M);
-    *bytes = w ? w->total_bytes() : 0;
-    return 0;
-}
-
-template <class U>
-int group_poly_live_workspaces(int* count)
-{
-    if (!count) return fail(HPCCG_HIP_EINVAL, "%s: NULL argument", U::who);
-    *count = g_ws<typename U::Workspace>.live();
-    return 0;
 }
 
 }  // namespace

@@ -1,40 +1,34 @@
 // hpccg_poly_host.h -- the host code of the Chebyshev polynomial preconditioned
 // CG, shared by the polynomial units (hpccg_poly.hip, hpccg_poly32.hip and,
 // under hpccg_poly_group_host.h, hpccg_poly_group.hip and
-// hpccg_poly32_group.hip): the workspace's polynomial state, the dispatch on a
-// chunk's columns and fp64 SpMM form, the kernel arguments, the launchers, the
-// checks of a caller's bounds and the interval with its coefficients; for the
-// one-rank units (poly, poly32) also the matrix check, the preconditioner, the
-// Gershgorin bound, the solve and the bodies of their extern "C" functions.
-// A unit hands over one traits struct U:
-//   Args, Workspace       its kernel arguments (a PolyArgs) and its workspace (a
-//                         PolyWorkspace)
+// hpccg_poly32_group.hip): the workspace's polynomial state, the kernel
+// arguments, the launchers with the degree in them, the checks of a caller's
+// bounds and the interval with its coefficients; for the one-rank units (poly,
+// poly32) also the Gershgorin bound, the per-call setup and the recurrence that
+// hpccg_onerank_host.h's solve runs, and the bodies of their bound and
+// last_spectrum exports. What is not polynomial -- the dispatch on a chunk's
+// columns and fp64 SpMM form, the init, SpMM and finalize launchers, the matrix
+// check, the preconditioner, the solve, the bookkeeping exports -- is
+// hpccg_onerank_host.h.
+// A unit hands over one traits struct U: what hpccg_onerank_host.h asks for
+// (Args a PolyArgs, Workspace a PolyWorkspace) and
 //   row0(w)               local row 0 inside a guarded column: the guard rows
 //                         (one rank) or the member's p0 (group)
-//   init, p<kR, kPre>, update<kR, kCheb>, finalize, spmm_a<kW, kR, kWaves>,
-//   spmm_sell<kR>         its kernels, as (templates of) kernel pointers; with
-//   step<kW, kR, kWaves>, step_sell<kR> where it runs the fp64 steps
+//   p<kR, kPre>, update<kR, kCheb>   its kernels, as templates of kernel
+//                         pointers; with step<kW, kR, kWaves>, step_sell<kR>
+//                         where it runs the fp64 steps
 // and a one-rank unit further
-//   who, solve_name       the name in front of its messages ("poly") and in
-//                         "the last <solve_name> solve"
-//   diag, check, q, bound, bound_top   the preconditioner's and the bound's kernels
+//   q, bound, bound_top   the bound's kernels
 //   launch_spmm(w, a, prologue), launch_step(w, a)   where poly32 differs: the
 //                         SpMM and one step over the chunks of columns
-// The __global__ entry points and the extern "C" definitions stay in the units.
-// The launchers are plain functions and the launch loops take them as function
-// pointers (hpccg_columns.h, hpccg_group.h); nothing here allocates per launch.
 // Internal linkage (each unit compiles its own copy), like hpccg_columns.h.
 #pragma once
 #include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <type_traits>
 
-#include "hpccg_columns.h"
-#include "hpccg_jacobi.h"
+#include "hpccg_onerank_host.h"
 #include "hpccg_poly_bodies.h"
 #include "hpccg_poly_coeffs.h"
-#include "hpccg_spmm.h"
 
 namespace hpccg {
 
@@ -77,35 +71,6 @@ struct PolyWorkspace : TraceWorkspace, JacobiCache {
     long long total_bytes() const { return bytes + rest_bytes; }
 };
 
-// f(std::integral_constant<int, kR>) for the chunk's column count R = 1, 2, 4.
-template <class F>
-void with_columns(int R, F f)
-{
-    if (R == 4)
-        f(std::integral_constant<int, 4>{});
-    else if (R == 2)
-        f(std::integral_constant<int, 2>{});
-    else
-        f(std::integral_constant<int, 1>{});
-}
-
-// The fp64 SpMM forms of a chunk (the pcg library's plan choices): f(width, kR,
-// kWaves), kWaves 5 for the 27-wide four-column form over images streamed from
-// HBM, else 4.
-template <class F>
-void with_spmm_form(const PolyArgs& a, int R, F f)
-{
-    using std::integral_constant;
-    if (a.a_width == 27 && R == 4 && a.nt)
-        f(integral_constant<int, 27>{}, integral_constant<int, 4>{}, integral_constant<int, 5>{});
-    else if (a.a_width == 27)
-        with_columns(R, [&](auto r) { f(integral_constant<int, 27>{}, r, integral_constant<int, 4>{}); });
-    else if (a.a_width == 7)
-        with_columns(R, [&](auto r) { f(integral_constant<int, 7>{}, r, integral_constant<int, 4>{}); });
-    else
-        with_columns(R, [&](auto r) { f(integral_constant<int, 0>{}, r, integral_constant<int, 4>{}); });
-}
-
 // z buffer `which` (0, 1): local row 0 of column 0
 template <class U>
 double* z_of(const typename U::Workspace* w, int which)
@@ -134,52 +99,18 @@ typename U::Args make_args(const typename U::Workspace* w, int nrhs, const doubl
     return a;
 }
 
-template <class U>
-void launch_init(const typename U::Workspace* w, const typename U::Args& a, int max_iter, double tol)
-{
-    hipLaunchKernelGGL(U::init, dim3((a.nrhs + 63) / 64), dim3(64), 0, w->v.stream, a, max_iter, tol);
-}
-
 // d == 0: z = m r in the register; else the last step's z (buffer d & 1, the
 // unit's own rows only) in r's place.
 template <class U>
 void launch_p(const typename U::Workspace* w, typename U::Args a, bool prologue)
 {
-    const dim3 g(a.grid), b(kBlock);
-    hipStream_t s = w->v.stream;
     const int d = w->degree;
     if (d > 0) {
         a.r = z_of<U>(w, d & 1);
         a.rcs = a.pcs;
     }
-    for_chunks(a.nrhs, true, [&](int c0, int R) {
-        a.c0 = c0;
-        with_columns(R, [&](auto r) {
-            if (d > 0)
-                hipLaunchKernelGGL((U::template p<decltype(r)::value, false>), g, b, 0, s, a, prologue);
-            else
-                hipLaunchKernelGGL((U::template p<decltype(r)::value, true>), g, b, 0, s, a, prologue);
-        });
-    });
-}
-
-// Ap = A p from the fp64 image.
-template <class U>
-void launch_spmm64(const typename U::Workspace* w, typename U::Args a, bool prologue)
-{
-    const dim3 g(a.grid), b(kBlock);
-    hipStream_t s = w->v.stream;
-    for_chunks(a.nrhs, true, [&](int c0, int R) {
-        a.c0 = c0;
-        if (!w->v.has_a)
-            with_columns(R, [&](auto r) {
-                hipLaunchKernelGGL((U::template spmm_sell<decltype(r)::value>), g, b, 0, s, a, prologue);
-            });
-        else
-            with_spmm_form(a, R, [&](auto wd, auto r, auto wv) {
-                hipLaunchKernelGGL((U::template spmm_a<decltype(wd)::value, decltype(r)::value, decltype(wv)::value>),
-                                   g, b, 0, s, a, prologue);
-            });
+    launch_chunks(w, a, prologue, [d](auto r) {
+        return d > 0 ? U::template p<decltype(r)::value, false> : U::template p<decltype(r)::value, true>;
     });
 }
 
@@ -187,18 +118,10 @@ void launch_spmm64(const typename U::Workspace* w, typename U::Args a, bool prol
 template <class U>
 void launch_update0(const typename U::Workspace* w, typename U::Args a, bool prologue)
 {
-    const dim3 g(a.grid), b(kBlock);
-    hipStream_t s = w->v.stream;
     const int d = w->degree;
     a.zout = z_of<U>(w, 0);
-    for_chunks(a.nrhs, true, [&](int c0, int R) {
-        a.c0 = c0;
-        with_columns(R, [&](auto r) {
-            if (d > 0)
-                hipLaunchKernelGGL((U::template update<decltype(r)::value, true>), g, b, 0, s, a, prologue);
-            else
-                hipLaunchKernelGGL((U::template update<decltype(r)::value, false>), g, b, 0, s, a, prologue);
-        });
+    launch_chunks(w, a, prologue, [d](auto r) {
+        return d > 0 ? U::template update<decltype(r)::value, true> : U::template update<decltype(r)::value, false>;
     });
 }
 
@@ -232,12 +155,6 @@ void launch_step64(const typename U::Workspace* w, typename U::Args a)
                                    b, 0, s, a);
             });
     });
-}
-
-template <class U>
-void launch_finalize(const typename U::Workspace* w, const typename U::Args& a, int which, int store_total)
-{
-    hipLaunchKernelGGL(U::finalize, dim3(a.nrhs), dim3(kFinThreads), 0, w->v.stream, a, which, store_total);
 }
 
 // A caller's bounds: each finite and >= 0 (0.0: the default); both given, lmin < lmax.
@@ -274,50 +191,6 @@ int resolve_interval(const char* who, int degree, double* lmin, double* lmax, do
 // ---------------------------------------------------------------------------
 // The one-rank units (poly, poly32)
 // ---------------------------------------------------------------------------
-inline long long p_column(const MatrixView& v)
-{
-    return (long long)v.npad + 2 * v.guard_rows;  // [guard | rows (padded) | guard]
-}
-
-// What a one-rank unit runs on: one rank, no halo.
-inline int check_matrix(const char* who, hpccg_hip_matrix* M, MatrixView* v)
-{
-    TRY(hpccg_hip_internal_view(M, v));
-    if (v->in_group)
-        return fail(HPCCG_HIP_EINVAL, "%s: the matrix is a member of an in-process group (one rank only)", who);
-    if (v->nranks > 1)
-        return fail(HPCCG_HIP_EINVAL, "%s: the matrix belongs to a communicator of %d ranks (one rank only)", who,
-                    v->nranks);
-    if (v->ghost_lo || v->ghost_hi) return fail(HPCCG_HIP_EINVAL, "%s: the matrix has halo rows (one rank only)", who);
-    if (!v->has_a && !v->has_sell) return fail(HPCCG_HIP_EINVAL, "%s: the matrix holds no device image", who);
-    return 0;
-}
-
-// Jacobi: the cached 1.0 / a_ii, or the refusal of a matrix it does not exist for.
-template <class U>
-int ensure_jacobi(typename U::Workspace* w)
-{
-    int row = -1;
-    TRY(build_jacobi(w, U::diag, &row));
-    if (row >= 0)
-        return fail(HPCCG_HIP_EINVAL,
-                    "%s: Jacobi needs a finite diagonal > 0 in every row; row %d is the first whose diagonal is "
-                    "missing, not finite or <= 0",
-                    U::who, row);
-    return 0;
-}
-
-// A call's own m: into the padded muser, every entry finite and > 0.
-template <class U>
-int stage_minv(typename U::Workspace* w, const double* minv, bool host)
-{
-    int row = -1;
-    TRY(load_minv(w, minv, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, U::check, &row));
-    if (row >= 0)
-        return fail(HPCCG_HIP_EINVAL, "%s: minv[%d] is not finite and > 0 (the first such entry)", U::who, row);
-    return 0;
-}
-
 // The bound's vectors (zeroed: q's guard zones and its rows past n are read and
 // never stored; a member's ghost planes by the halo only). pcs: the guarded column.
 int ensure_bound_vectors(PolyWorkspace* w, long long pcs)
@@ -407,8 +280,9 @@ int run_cg(typename U::Workspace* w, int nrhs, const double* m, int max_iter, do
     return finish_recurrence(w, nrhs, niters, normr, wall);
 }
 
-// prepare (may be null): what the unit builds per matrix before the
-// preconditioner (poly32: the fp32 image, whose verdict comes first).
+// The solve: hpccg_onerank_host.h's, with the degree and the bounds checked
+// before the matrix and the interval resolved once m is in hand. prepare (may
+// be null): poly32's image.
 template <class U>
 int solve_common(hpccg_hip_matrix* M, int nrhs, const double* B, long long ldb, double* X, long long ldx,
                  const double* minv, int degree, double lmin, double lmax, int max_iter, double tol, int* niters,
@@ -416,69 +290,29 @@ int solve_common(hpccg_hip_matrix* M, int nrhs, const double* B, long long ldb, 
 {
     using W = typename U::Workspace;
     const char* who = U::who;
-    if (!M || !B || !X || !niters || !normr) return fail(HPCCG_HIP_EINVAL, "%s: NULL argument", who);
-    if (nrhs <= 0) return fail(HPCCG_HIP_EINVAL, "%s: nrhs %d (at least 1)", who, nrhs);
-    if (max_iter < 0) return fail(HPCCG_HIP_EINVAL, "%s: max_iter %d is negative", who, max_iter);
-    // (below every row count, so refused before the matrix is looked at)
-    if (ldb < 0 || ldx < 0)
-        return fail(HPCCG_HIP_EINVAL, "%s: leading dimensions %lld, %lld are negative", who, ldb, ldx);
-    if (degree < 0 || degree > kPolyMaxDegree)
-        return fail(HPCCG_HIP_EINVAL, "%s: degree %d (0 to %d)", who, degree, kPolyMaxDegree);
-    TRY(check_bounds(who, lmin, lmax));
-    MatrixView v;
-    TRY(check_matrix(who, M, &v));
-    if (ldb < v.n || ldx < v.n)
-        return fail(HPCCG_HIP_EINVAL, "%s: leading dimensions %lld, %lld below the %d rows", who, ldb, ldx, v.n);
-    if (times) std::fill(times, times + 7, 0.0);
-    if (v.n == 0) {
-        for (int c = 0; c < nrhs; c++) {
-            niters[c] = 0;
-            normr[c] = 0.0;
-        }
-        return 0;
-    }
-    if (max_iter < 1) max_iter = 1;
-    return keep_device([&]() -> int {
-        W* w = nullptr;
-        TRY(g_ws<W>.record(M, v, &w));
-        // the unit's own first, then the preconditioner: a refused call leaves X as it is
-        if (prepare) TRY(prepare(w));
-        TRY(ensure_cache(w));
-        if (minv)
-            TRY(stage_minv<U>(w, minv, host));
-        else
-            TRY(ensure_jacobi<U>(w));
-        const double* m = minv ? w->muser : w->jac;
-        TRY(resolve_interval(who, degree, &lmin, &lmax, &w->cheb0, w->aj, w->bj, [&](double* top) {
-            return minv ? compute_bound<U>(w, m, top) : jacobi_bound<U>(w, top);
-        }));
-        TRY(ensure_vectors(w, nrhs, max_iter, p_column(v), 0));
-        w->degree = degree;
-        w->last_lmin = lmin;
-        w->last_lmax = lmax;
-        w->solved = true;
-        const hipMemcpyKind in = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-        const hipMemcpyKind out = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-        const auto t0 = std::chrono::steady_clock::now();
-        TRY(copy_cols(w, w->b, w->vcs, B, ldb, nrhs, in));
-        TRY(copy_cols(w, w->x, w->vcs, X, ldx, nrhs, in));
-        if (host) HIP_TRY(hipStreamSynchronize(v.stream));
-        const auto t1 = std::chrono::steady_clock::now();
-        double wall = 0.0;
-        TRY(run_cg<U>(w, nrhs, m, max_iter, tol, niters, normr, &wall));
-        const auto t2 = std::chrono::steady_clock::now();
-        TRY(copy_cols(w, X, ldx, w->x, w->vcs, nrhs, out));
-        HIP_TRY(hipStreamSynchronize(v.stream));
-        const auto t3 = std::chrono::steady_clock::now();
-        if (times) {
-            times[0] = wall;
-            if (host) times[6] = std::chrono::duration<double>((t1 - t0) + (t3 - t2)).count();
-        }
-        return 0;
-    });
+    return solve_onerank<U>(
+        M, nrhs, B, ldb, X, ldx, minv, max_iter, tol, niters, normr, times, host,
+        [&]() -> int {
+            if (degree < 0 || degree > kPolyMaxDegree)
+                return fail(HPCCG_HIP_EINVAL, "%s: degree %d (0 to %d)", who, degree, kPolyMaxDegree);
+            return check_bounds(who, lmin, lmax);
+        },
+        prepare,
+        [&](W* w, const double* m, int kmax) -> int {
+            TRY(resolve_interval(who, degree, &lmin, &lmax, &w->cheb0, w->aj, w->bj, [&](double* top) {
+                return minv ? compute_bound<U>(w, m, top) : jacobi_bound<U>(w, top);
+            }));
+            TRY(ensure_vectors(w, nrhs, kmax, p_column(w->v), 0));
+            w->degree = degree;
+            w->last_lmin = lmin;
+            w->last_lmax = lmax;
+            w->solved = true;
+            return 0;
+        },
+        run_cg<U>);
 }
 
-// The bodies of a one-rank unit's extern "C" functions beside the solves.
+// The bodies of a one-rank unit's bound and last_spectrum exports.
 template <class U>
 int poly_bound(hpccg_hip_matrix* M, const double* minv_dev, double* lmax)
 {
@@ -512,43 +346,6 @@ int poly_last_spectrum(const hpccg_hip_matrix* M, double* lmin, double* lmax)
         return fail(HPCCG_HIP_EINVAL, "%s: no spectrum (no %s solve ran on the matrix)", U::who, U::solve_name);
     *lmin = w->last_lmin;
     *lmax = w->last_lmax;
-    return 0;
-}
-
-template <class U>
-int poly_last_trace(const hpccg_hip_matrix* M, int col, double* out, int cap)
-{
-    if (!M || !out) return fail(HPCCG_HIP_EINVAL, "%s: NULL argument", U::who);
-    const typename U::Workspace* w = g_ws<typename U::Workspace>.find(M);
-    const int n = copy_trace(w, col, out, cap);
-    if (n < 0)
-        return fail(HPCCG_HIP_EINVAL, "%s: no trace of column %d (the last %s solve had %d)", U::who, col,
-                    U::solve_name, w ? (int)w->trace.size() : 0);
-    return n;
-}
-
-template <class U>
-int poly_release(hpccg_hip_matrix* M)
-{
-    if (!M) return fail(HPCCG_HIP_EINVAL, "%s: NULL argument", U::who);
-    g_ws<typename U::Workspace>.drop(M);
-    return 0;
-}
-
-template <class U>
-int poly_workspace_bytes(const hpccg_hip_matrix* M, long long* bytes)
-{
-    if (!M || !bytes) return fail(HPCCG_HIP_EINVAL, "%s: NULL argument", U::who);
-    const typename U::Workspace* w = g_ws<typename U::Workspace>.find(M);
-    *bytes = w ? w->total_bytes() : 0;
-    return 0;
-}
-
-template <class U>
-int poly_live_workspaces(int* count)
-{
-    if (!count) return fail(HPCCG_HIP_EINVAL, "%s: NULL argument", U::who);
-    *count = g_ws<typename U::Workspace>.live();
     return 0;
 }
 

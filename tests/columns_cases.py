@@ -103,9 +103,10 @@ def fp32_image(A):
     return oracle.CSR(A.row_ptr, A.cols, A.vals.astype(np.float32).astype(np.float64), None, None, None)
 
 
-def expect_refined(A, b, x0, max_iter, tol, max_sweeps=8, inner_rtol=2.0 ** -20):
+def expect_refined(A, b, x0, max_iter, tol, max_sweeps=8, inner_rtol=2.0 ** -20, dot=oracle.ddot):
     """include/hpccg_hip_mixed.h, steps 1 to 4, restated: (x, niters, normr,
-    inner trace, (sweep iters, sweep residuals))."""
+    inner trace, (sweep iters, sweep residuals)). dot: the order of every sum
+    (the sequential one by default)."""
     A32 = fp32_image(A)
     ones = np.ones(A.nrow)
     x = np.array(x0, np.float64)
@@ -115,11 +116,11 @@ def expect_refined(A, b, x0, max_iter, tol, max_sweeps=8, inner_rtol=2.0 ** -20)
     with np.errstate(all="ignore"):
         while True:
             r = b + (-1.0) * oracle.sparsemv(A, x)
-            rho = np.sqrt(np.float64(oracle.ddot(r, r)))
+            rho = np.sqrt(np.float64(dot(r, r)))
             resid.append(rho)
             if rho <= tol or not np.isfinite(rho) or rho == 0.0 or s == max_sweeps or left == 0:
                 break
-            d, it, _, tr = restated(A32, r, ones, left + 1, max(tol, inner_rtol * rho))
+            d, it, _, tr = restated(A32, r, ones, left + 1, max(tol, inner_rtol * rho), dot=dot)
             x = x + d
             iters.append(it)
             trace.extend(tr)

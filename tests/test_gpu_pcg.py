@@ -131,18 +131,19 @@ def pcg_solve(hp, gpu, M, B, X0, max_iter, tol=0.0, minv=None, ld=None):
 
 # ---------------------------------------------------------------------------
 # The recurrence of include/hpccg_hip_pcg.h restated: oracle.sparsemv and a
-# fixed-order (sequential) float64 dot. trace[k] is the normr iteration k
+# fixed-order (sequential) float64 dot by default (dot: another order, for the
+# restatement's own error). trace[k] is the normr iteration k
 # reports, sqrt(rr_{k-1}) (HPCCG.cpp:358), as in every solver here.
 # ---------------------------------------------------------------------------
-def restated(A, b, minv, max_iter, tol=0.0, x0=None):
+def restated(A, b, minv, max_iter, tol=0.0, x0=None, dot=oracle.ddot):
     with np.errstate(all="ignore"):
         x = np.zeros(A.nrow) if x0 is None else np.array(x0, np.float64)
         p = x + 0.0 * x
         Ap = oracle.sparsemv(A, p)
         r = b + (-1.0) * Ap
-        rz = np.float64(oracle.ddot(r, minv * r))
+        rz = np.float64(dot(r, minv * r))
         oldrz = rz
-        hist = [np.float64(oracle.ddot(r, r))]
+        hist = [np.float64(dot(r, r))]
         normr = np.sqrt(hist[0])
         trace = [normr]
         k = 1
@@ -152,12 +153,12 @@ def restated(A, b, minv, max_iter, tol=0.0, x0=None):
             normr = np.sqrt(hist[k - 1])
             trace.append(normr)
             Ap = oracle.sparsemv(A, p)
-            alpha = rz / np.float64(oracle.ddot(p, Ap))
+            alpha = rz / np.float64(dot(p, Ap))
             x = x + alpha * p
             r = r + (-alpha) * Ap
             oldrz = rz
-            rz = np.float64(oracle.ddot(r, minv * r))
-            hist.append(np.float64(oracle.ddot(r, r)))
+            rz = np.float64(dot(r, minv * r))
+            hist.append(np.float64(dot(r, r)))
             k += 1
     return x, k - 1, float(normr), np.array(trace)
 

@@ -273,6 +273,23 @@ def pcg_group_lib() -> C.CDLL:
     })
 
 
+SRCG_GROUP_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_srcg_group.so")
+
+
+def srcg_group_lib() -> C.CDLL:
+    """Load libhpccg_hip_srcg_group.so (include/hpccg_hip_srcg_group.h) on first
+    use. It is linked against libhpccg_hip.so beside it, so lib() is loaded
+    first and both share one copy of the main library."""
+    return _load_unit("srcg_group", SRCG_GROUP_LIB_PATH, "the group srcg library", "the group single-reduction solve has no fallback", {
+        "hpccg_hip_group_srcg_abi_version": (_ip, []),
+        "hpccg_hip_group_srcg_solve_device": (_ip, [_PV, _ip, _ip, _PV, _PL, _PV, _PL, _PV, _ip, _dp, _PI, _PD, _PD]),
+        "hpccg_hip_group_srcg_last_trace": (_ip, [_PV, _ip, _ip, _PD, _ip]),
+        "hpccg_hip_group_srcg_release": (_ip, [_vp]),
+        "hpccg_hip_group_srcg_workspace_bytes": (_ip, [_vp, _PL]),
+        "hpccg_hip_group_srcg_live_workspaces": (_ip, [_PI]),
+    })
+
+
 POLY_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_poly.so")
 
 
@@ -393,6 +410,11 @@ def pcg_exported_symbols() -> list[str]:
 def srcg_exported_symbols() -> list[str]:
     """Functions include/hpccg_hip_srcg.h declares (checked by the CPU suite)."""
     return _declared("hpccg_hip_srcg.h", r"\b(hpccg_hip_srcg_\w+)\s*\(")
+
+
+def group_srcg_exported_symbols() -> list[str]:
+    """Functions include/hpccg_hip_srcg_group.h declares (checked by the CPU suite)."""
+    return _declared("hpccg_hip_srcg_group.h", r"\b(hpccg_hip_group_srcg_\w+)\s*\(")
 
 
 def mixed_exported_symbols() -> list[str]:
@@ -1567,6 +1589,71 @@ def group_poly32_release(M: Matrix) -> None:
 def group_poly32_live_workspaces() -> int:
     """Matrices that hold a group poly32 workspace (0 when the library was never loaded)."""
     return _live("poly32_group", "group_poly32_live_workspaces")
+
+
+# ---------------------------------------------------------------------------
+# single-reduction preconditioned solve over an in-process group (include/hpccg_hip_srcg_group.h)
+# ---------------------------------------------------------------------------
+_SRCG_HALO_COPIES_ENV = "HPCCG_GROUP_SRCG_HALO_COPIES"
+
+
+def group_HPCCG_srcg(Ms: list, Bs, Xs, max_iter: int = 500, tolerance: float = 0.0, minvs=None, nrhs=None, ldb=None,
+                     ldx=None, halo_copies: bool = False):
+    """nrhs single-reduction preconditioned CG solves over an in-process group
+    with M^-1 = diag(minv) (hpccg_hip_group_srcg_solve_device): group_HPCCG_pcg's
+    method with one sum over the members per iteration instead of two. The
+    first iteration (max_iter <= 2) is group_HPCCG_pcg bit for bit; a group of
+    one is HPCCG_srcg bit for bit. Ms, Bs, Xs, minvs: as group_HPCCG_pcg. Xs is
+    updated in place. halo_copies (diagnostic): move the ghost planes of u by
+    one copy per column and side instead of one kernel launch per member; the
+    bits are the same. Returns (niters[nrhs], normr[nrhs], times)."""
+    L = srcg_group_lib()
+    P = len(Ms)
+    if len(Bs) != P or len(Xs) != P:
+        raise HPCCGError(f"{P} members, {len(Bs)} B and {len(Xs)} X column sets")
+    hs = (C.c_void_p * P)(*[M.h for M in Ms])
+    bp, nb, ldb_ = _group_cols(Bs, nrhs, ldb, "Bs")
+    xp, nx_, ldx_ = _group_cols(Xs, nrhs, ldx, "Xs")
+    if nb != nx_:
+        raise HPCCGError(f"Bs holds {nb} columns, Xs {nx_}")
+    mp = _group_minvs(Ms, minvs)
+    it = np.zeros(max(nb, 1), np.int32)
+    nr = np.zeros(max(nb, 1), np.float64)
+    times = np.zeros(7, np.float64)
+    with _halo_copies_env(halo_copies, _SRCG_HALO_COPIES_ENV):
+        rc = L.hpccg_hip_group_srcg_solve_device(hs, P, nb, bp, ldb_, xp, ldx_, mp, max_iter, tolerance,
+                                                 it.ctypes.data_as(C.POINTER(C.c_int)),
+                                                 nr.ctypes.data_as(C.POINTER(C.c_double)),
+                                                 times.ctypes.data_as(C.POINTER(C.c_double)))
+    _check(rc, "group_HPCCG_srcg")
+    return it[:nb], nr[:nb], times
+
+
+def group_last_trace_srcg(Ms: list, col: int, cap: int = 100000) -> np.ndarray:
+    """Residual trace (norm of r) of column col of the last group_HPCCG_srcg on Ms."""
+    P = len(Ms)
+    hs = (C.c_void_p * P)(*[M.h for M in Ms])
+    out = np.zeros(cap, np.float64)
+    n = srcg_group_lib().hpccg_hip_group_srcg_last_trace(hs, P, int(col), out.ctypes.data_as(C.POINTER(C.c_double)),
+                                                         cap)
+    if n < 0:
+        _check(n, "group_last_trace_srcg")
+    return out[:n]
+
+
+def group_srcg_workspace_bytes(M: Matrix) -> int:
+    """Device bytes member M's group srcg workspace holds (0: none)."""
+    return _workspace_bytes("srcg_group", "group_srcg_workspace_bytes", M.h)
+
+
+def group_srcg_release(M: Matrix) -> None:
+    """Free member M's group srcg workspace (with its cached 1 / a_ii) now (close() does it too)."""
+    _release("srcg_group", "group_srcg_release", M.h)
+
+
+def group_srcg_live_workspaces() -> int:
+    """Matrices that hold a group srcg workspace (0 when the library was never loaded)."""
+    return _live("srcg_group", "group_srcg_live_workspaces")
 
 
 def HPC_sparsemv(M: Matrix, x, y) -> int:

@@ -1196,7 +1196,7 @@ def group_HPCCG(Ms: list, bs, xs, max_iter: int = 500, tolerance: float = 0.0):
     """HPCCG() over an in-process group; bs[r], xs[r]: rank r's device vectors
     (xs updated in place). Returns (ierr, niters, normr, times)."""
     P = len(Ms)
-    hs = (C.c_void_p * P)(*[M.h for M in Ms])
+    hs = _handles(Ms)
     bp = (C.c_void_p * P)(*[_ptr(b) for b in bs])
     xp = (C.c_void_p * P)(*[_ptr(x) for x in xs])
     it = C.c_int(0)
@@ -1225,6 +1225,102 @@ def _group_cols(As, nrhs, lds, what):
     return ptrs, (got[0][1] if got else 0), ld
 
 
+def _handles(Ms):
+    return (C.c_void_p * len(Ms))(*[M.h for M in Ms])
+
+
+def _group_operands(Ms, Bs, Xs, nrhs, ldb, ldx):
+    """What every group solve takes first -- the handles, P, nrhs, the column
+    sets of B and of X with their leading dimensions -- with the counts of
+    column sets and of columns checked."""
+    P = len(Ms)
+    if len(Bs) != P or len(Xs) != P:
+        raise HPCCGError(f"{P} members, {len(Bs)} B and {len(Xs)} X column sets")
+    bp, nb, ldb_ = _group_cols(Bs, nrhs, ldb, "Bs")
+    xp, nx_, ldx_ = _group_cols(Xs, nrhs, ldx, "Xs")
+    if nb != nx_:
+        raise HPCCGError(f"Bs holds {nb} columns, Xs {nx_}")
+    return _handles(Ms), P, nb, bp, ldb_, xp, ldx_
+
+
+def _group_call(what, solve, operands, *rest):
+    """The call of a group library's solve_device (rest: its arguments between
+    ldx and niters) and the result (niters[nrhs], normr[nrhs], times)."""
+    nb = operands[2]
+    it = np.zeros(max(nb, 1), np.int32)
+    nr = np.zeros(max(nb, 1), np.float64)
+    times = np.zeros(7, np.float64)
+    rc = solve(*operands, *rest, it.ctypes.data_as(C.POINTER(C.c_int)), nr.ctypes.data_as(C.POINTER(C.c_double)),
+               times.ctypes.data_as(C.POINTER(C.c_double)))
+    _check(rc, what)
+    return it[:nb], nr[:nb], times
+
+
+def _group_minvs(Ms, minvs):
+    """The array of the members' device m pointers (None: Jacobi)."""
+    if minvs is None:
+        return None
+    P = len(Ms)
+    if len(minvs) != P:
+        raise HPCCGError(f"{P} members, {len(minvs)} minv vectors")
+    ptrs = []
+    for r, (M, m) in enumerate(zip(Ms, minvs)):
+        nrow = int(M.info()["nrow"])
+        if not isinstance(m, int) and (m.dim() != 1 or m.shape[0] < nrow or (m.shape[0] > 1 and m.stride(0) != 1)):
+            raise HPCCGError(f"minvs[{r}]: a contiguous 1-D tensor of {nrow} entries")
+        ptrs.append(_ptr(m))
+    return (C.c_void_p * P)(*ptrs)
+
+
+class _halo_copies_env:
+    """A library's halo-by-copies switch set (or cleared) for one call."""
+
+    def __init__(self, on, name):
+        self.on = on
+        self.name = name
+
+    def __enter__(self):
+        self.saved = os.environ.pop(self.name, None)
+        if self.on:
+            os.environ[self.name] = "1"
+
+    def __exit__(self, *exc):
+        os.environ.pop(self.name, None)
+        if self.saved is not None:
+            os.environ[self.name] = self.saved
+
+
+def _group_solve(what, solve, env, Ms, Bs, Xs, minvs, nrhs, ldb, ldx, halo_copies, *rest):
+    """What the preconditioned group solves share: _group_operands, the
+    members' minvs, the library's halo-by-copies switch env around the call of
+    solve (rest: its arguments between minv and niters) and the result
+    (niters[nrhs], normr[nrhs], times)."""
+    operands = _group_operands(Ms, Bs, Xs, nrhs, ldb, ldx)
+    mp = _group_minvs(Ms, minvs)
+    with _halo_copies_env(halo_copies, env):
+        return _group_call(what, solve, operands, mp, *rest)
+
+
+def _group_last_trace(what, last_trace, Ms, col, cap):
+    out = np.zeros(cap, np.float64)
+    n = last_trace(_handles(Ms), len(Ms), int(col), out.ctypes.data_as(C.POINTER(C.c_double)), cap)
+    if n < 0:
+        _check(n, what)
+    return out[:n]
+
+
+def _group_bound(what, bound, Ms, minvs):
+    v = C.c_double(0.0)
+    _check(bound(_handles(Ms), len(Ms), _group_minvs(Ms, minvs), C.byref(v)), what)
+    return v.value
+
+
+def _group_last_spectrum(what, last_spectrum, Ms):
+    lo, hi = C.c_double(0.0), C.c_double(0.0)
+    _check(last_spectrum(_handles(Ms), len(Ms), C.byref(lo), C.byref(hi)), what)
+    return lo.value, hi.value
+
+
 def group_HPCCG_batch(Ms: list, Bs, Xs, max_iter: int = 500, tolerance: float = 0.0, nrhs=None, ldb=None,
                       ldx=None):
     """nrhs CG solves over an in-process group in one pass over the matrix per
@@ -1234,24 +1330,8 @@ def group_HPCCG_batch(Ms: list, Bs, Xs, max_iter: int = 500, tolerance: float = 
     (ld >= the member's nrow) -- tensors, or device pointers with nrhs and the
     leading dimensions. Xs is updated in place. Returns
     (niters[nrhs], normr[nrhs], times)."""
-    L = batch_lib()
-    P = len(Ms)
-    if len(Bs) != P or len(Xs) != P:
-        raise HPCCGError(f"{P} members, {len(Bs)} B and {len(Xs)} X column sets")
-    hs = (C.c_void_p * P)(*[M.h for M in Ms])
-    bp, nb, ldb_ = _group_cols(Bs, nrhs, ldb, "Bs")
-    xp, nx_, ldx_ = _group_cols(Xs, nrhs, ldx, "Xs")
-    if nb != nx_:
-        raise HPCCGError(f"Bs holds {nb} columns, Xs {nx_}")
-    it = np.zeros(max(nb, 1), np.int32)
-    nr = np.zeros(max(nb, 1), np.float64)
-    times = np.zeros(7, np.float64)
-    rc = L.hpccg_hip_group_batch_solve_device(hs, P, nb, bp, ldb_, xp, ldx_, max_iter, tolerance,
-                                              it.ctypes.data_as(C.POINTER(C.c_int)),
-                                              nr.ctypes.data_as(C.POINTER(C.c_double)),
-                                              times.ctypes.data_as(C.POINTER(C.c_double)))
-    _check(rc, "group_HPCCG_batch")
-    return it[:nb], nr[:nb], times
+    solve = batch_lib().hpccg_hip_group_batch_solve_device
+    return _group_call("group_HPCCG_batch", solve, _group_operands(Ms, Bs, Xs, nrhs, ldb, ldx), max_iter, tolerance)
 
 
 def group_sparsemv_batch(Ms: list, Xs, Ys, nrhs=None, ldx=None, ldy=None) -> int:
@@ -1260,7 +1340,7 @@ def group_sparsemv_batch(Ms: list, Xs, Ys, nrhs=None, ldx=None, ldy=None) -> int
     P = len(Ms)
     if len(Xs) != P or len(Ys) != P:
         raise HPCCGError(f"{P} members, {len(Xs)} X and {len(Ys)} Y column sets")
-    hs = (C.c_void_p * P)(*[M.h for M in Ms])
+    hs = _handles(Ms)
     xp, nx_, ldx_ = _group_cols(Xs, nrhs, ldx, "Xs")
     yp, ny_, ldy_ = _group_cols(Ys, nrhs, ldy, "Ys")
     if nx_ != ny_:
@@ -1271,21 +1351,12 @@ def group_sparsemv_batch(Ms: list, Xs, Ys, nrhs=None, ldx=None, ldy=None) -> int
 
 def group_last_trace_batch(Ms: list, col: int, cap: int = 100000) -> np.ndarray:
     """Residual trace of column col of the last group_HPCCG_batch on Ms."""
-    P = len(Ms)
-    hs = (C.c_void_p * P)(*[M.h for M in Ms])
-    out = np.zeros(cap, np.float64)
-    n = batch_lib().hpccg_hip_group_batch_last_trace(hs, P, int(col), out.ctypes.data_as(C.POINTER(C.c_double)),
-                                                     cap)
-    if n < 0:
-        _check(n, "group_last_trace_batch")
-    return out[:n]
+    return _group_last_trace("group_last_trace_batch", batch_lib().hpccg_hip_group_batch_last_trace, Ms, col, cap)
 
 
 # ---------------------------------------------------------------------------
 # preconditioned solve over an in-process group (include/hpccg_hip_pcg_group.h)
 # ---------------------------------------------------------------------------
-_HALO_COPIES_ENV = "HPCCG_GROUP_PCG_HALO_COPIES"
-
 
 def group_HPCCG_pcg(Ms: list, Bs, Xs, max_iter: int = 500, tolerance: float = 0.0, minvs=None, nrhs=None, ldb=None,
                     ldx=None, halo_copies: bool = False):
@@ -1299,33 +1370,9 @@ def group_HPCCG_pcg(Ms: list, Bs, Xs, max_iter: int = 500, tolerance: float = 0.
     the ghost planes by one copy per column and side, as the group batch does,
     instead of one kernel launch per member; the bits are the same. Returns
     (niters[nrhs], normr[nrhs], times)."""
-    L = pcg_group_lib()
-    P = len(Ms)
-    if len(Bs) != P or len(Xs) != P:
-        raise HPCCGError(f"{P} members, {len(Bs)} B and {len(Xs)} X column sets")
-    hs = (C.c_void_p * P)(*[M.h for M in Ms])
-    bp, nb, ldb_ = _group_cols(Bs, nrhs, ldb, "Bs")
-    xp, nx_, ldx_ = _group_cols(Xs, nrhs, ldx, "Xs")
-    if nb != nx_:
-        raise HPCCGError(f"Bs holds {nb} columns, Xs {nx_}")
-    mp = _group_minvs(Ms, minvs)
-    it = np.zeros(max(nb, 1), np.int32)
-    nr = np.zeros(max(nb, 1), np.float64)
-    times = np.zeros(7, np.float64)
-    saved = os.environ.pop(_HALO_COPIES_ENV, None)
-    if halo_copies:
-        os.environ[_HALO_COPIES_ENV] = "1"
-    try:
-        rc = L.hpccg_hip_group_pcg_solve_device(hs, P, nb, bp, ldb_, xp, ldx_, mp, max_iter, tolerance,
-                                                it.ctypes.data_as(C.POINTER(C.c_int)),
-                                                nr.ctypes.data_as(C.POINTER(C.c_double)),
-                                                times.ctypes.data_as(C.POINTER(C.c_double)))
-    finally:
-        os.environ.pop(_HALO_COPIES_ENV, None)
-        if saved is not None:
-            os.environ[_HALO_COPIES_ENV] = saved
-    _check(rc, "group_HPCCG_pcg")
-    return it[:nb], nr[:nb], times
+    return _group_solve("group_HPCCG_pcg", pcg_group_lib().hpccg_hip_group_pcg_solve_device,
+                        "HPCCG_GROUP_PCG_HALO_COPIES", Ms, Bs, Xs, minvs, nrhs, ldb, ldx, halo_copies, max_iter,
+                        tolerance)
 
 
 def group_pcg_diagonal(Ms: list) -> list:
@@ -1333,7 +1380,7 @@ def group_pcg_diagonal(Ms: list) -> list:
     reads it from the member's device image (0.0 where a row stores none)."""
     import torch
     P = len(Ms)
-    hs = (C.c_void_p * P)(*[M.h for M in Ms])
+    hs = _handles(Ms)
     ns = [int(M.info()["nrow"]) for M in Ms]
     ds = [torch.zeros(max(n, 1), dtype=torch.float64, device="cuda") for n in ns]
     dp = (C.c_void_p * P)(*[_ptr(d) for d in ds])
@@ -1343,14 +1390,7 @@ def group_pcg_diagonal(Ms: list) -> list:
 
 def group_last_trace_pcg(Ms: list, col: int, cap: int = 100000) -> np.ndarray:
     """Residual trace (norm of r) of column col of the last group_HPCCG_pcg on Ms."""
-    P = len(Ms)
-    hs = (C.c_void_p * P)(*[M.h for M in Ms])
-    out = np.zeros(cap, np.float64)
-    n = pcg_group_lib().hpccg_hip_group_pcg_last_trace(hs, P, int(col), out.ctypes.data_as(C.POINTER(C.c_double)),
-                                                       cap)
-    if n < 0:
-        _check(n, "group_last_trace_pcg")
-    return out[:n]
+    return _group_last_trace("group_last_trace_pcg", pcg_group_lib().hpccg_hip_group_pcg_last_trace, Ms, col, cap)
 
 
 def group_pcg_workspace_bytes(M: Matrix) -> int:
@@ -1371,41 +1411,9 @@ def group_pcg_live_workspaces() -> int:
 # ---------------------------------------------------------------------------
 # polynomial preconditioned solve over an in-process group (include/hpccg_hip_poly_group.h)
 # ---------------------------------------------------------------------------
-_POLY_HALO_COPIES_ENV = "HPCCG_GROUP_POLY_HALO_COPIES"
-
-
-def _group_minvs(Ms, minvs):
-    """The array of the members' device m pointers (None: Jacobi)."""
-    if minvs is None:
-        return None
-    P = len(Ms)
-    if len(minvs) != P:
-        raise HPCCGError(f"{P} members, {len(minvs)} minv vectors")
-    ptrs = []
-    for r, (M, m) in enumerate(zip(Ms, minvs)):
-        nrow = int(M.info()["nrow"])
-        if not isinstance(m, int) and (m.dim() != 1 or m.shape[0] < nrow or (m.shape[0] > 1 and m.stride(0) != 1)):
-            raise HPCCGError(f"minvs[{r}]: a contiguous 1-D tensor of {nrow} entries")
-        ptrs.append(_ptr(m))
-    return (C.c_void_p * P)(*ptrs)
-
-
-class _halo_copies_env:
-    """The library's halo-by-copies switch set (or cleared) for one call."""
-
-    def __init__(self, on, name=_POLY_HALO_COPIES_ENV):
-        self.on = on
-        self.name = name
-
-    def __enter__(self):
-        self.saved = os.environ.pop(self.name, None)
-        if self.on:
-            os.environ[self.name] = "1"
-
-    def __exit__(self, *exc):
-        os.environ.pop(self.name, None)
-        if self.saved is not None:
-            os.environ[self.name] = self.saved
+def _interval(degree, lmin, lmax):
+    """degree, lmin, lmax as the polynomial libraries take them (0.0: the default)."""
+    return int(degree), 0.0 if lmin is None else float(lmin), 0.0 if lmax is None else float(lmax)
 
 
 def group_HPCCG_poly(Ms: list, Bs, Xs, degree: int = 2, lmin=None, lmax=None, minvs=None, max_iter: int = 500,
@@ -1419,62 +1427,26 @@ def group_HPCCG_poly(Ms: list, Bs, Xs, degree: int = 2, lmin=None, lmax=None, mi
     (diagnostic): move every ghost plane of z and p by one copy per column and
     side instead of one kernel launch per member; the bits are the same.
     Returns (niters[nrhs], normr[nrhs], times)."""
-    L = poly_group_lib()
-    P = len(Ms)
-    if len(Bs) != P or len(Xs) != P:
-        raise HPCCGError(f"{P} members, {len(Bs)} B and {len(Xs)} X column sets")
-    hs = (C.c_void_p * P)(*[M.h for M in Ms])
-    bp, nb, ldb_ = _group_cols(Bs, nrhs, ldb, "Bs")
-    xp, nx_, ldx_ = _group_cols(Xs, nrhs, ldx, "Xs")
-    if nb != nx_:
-        raise HPCCGError(f"Bs holds {nb} columns, Xs {nx_}")
-    mp = _group_minvs(Ms, minvs)
-    it = np.zeros(max(nb, 1), np.int32)
-    nr = np.zeros(max(nb, 1), np.float64)
-    times = np.zeros(7, np.float64)
-    with _halo_copies_env(halo_copies):
-        rc = L.hpccg_hip_group_poly_solve_device(hs, P, nb, bp, ldb_, xp, ldx_, mp, int(degree),
-                                                 0.0 if lmin is None else float(lmin),
-                                                 0.0 if lmax is None else float(lmax), max_iter, tolerance,
-                                                 it.ctypes.data_as(C.POINTER(C.c_int)),
-                                                 nr.ctypes.data_as(C.POINTER(C.c_double)),
-                                                 times.ctypes.data_as(C.POINTER(C.c_double)))
-    _check(rc, "group_HPCCG_poly")
-    return it[:nb], nr[:nb], times
+    return _group_solve("group_HPCCG_poly", poly_group_lib().hpccg_hip_group_poly_solve_device,
+                        "HPCCG_GROUP_POLY_HALO_COPIES", Ms, Bs, Xs, minvs, nrhs, ldb, ldx, halo_copies,
+                        *_interval(degree, lmin, lmax), max_iter, tolerance)
 
 
 def group_poly_bound(Ms: list, minvs=None) -> float:
     """The symmetric Gershgorin bound of the group's global matrix that
     group_HPCCG_poly takes for lmax; minvs: per member a device tensor / pointer
     of its nrow entries, or None for Jacobi."""
-    P = len(Ms)
-    hs = (C.c_void_p * P)(*[M.h for M in Ms])
-    v = C.c_double(0.0)
-    _check(poly_group_lib().hpccg_hip_group_poly_bound(hs, P, _group_minvs(Ms, minvs), C.byref(v)),
-           "group_poly_bound")
-    return v.value
+    return _group_bound("group_poly_bound", poly_group_lib().hpccg_hip_group_poly_bound, Ms, minvs)
 
 
 def group_last_trace_poly(Ms: list, col: int, cap: int = 100000) -> np.ndarray:
     """Residual trace (norm of r) of column col of the last group_HPCCG_poly on Ms."""
-    P = len(Ms)
-    hs = (C.c_void_p * P)(*[M.h for M in Ms])
-    out = np.zeros(cap, np.float64)
-    n = poly_group_lib().hpccg_hip_group_poly_last_trace(hs, P, int(col), out.ctypes.data_as(C.POINTER(C.c_double)),
-                                                         cap)
-    if n < 0:
-        _check(n, "group_last_trace_poly")
-    return out[:n]
+    return _group_last_trace("group_last_trace_poly", poly_group_lib().hpccg_hip_group_poly_last_trace, Ms, col, cap)
 
 
 def group_last_spectrum_poly(Ms: list) -> tuple:
     """(lmin, lmax) the last group_HPCCG_poly on Ms used."""
-    P = len(Ms)
-    hs = (C.c_void_p * P)(*[M.h for M in Ms])
-    lo, hi = C.c_double(0.0), C.c_double(0.0)
-    _check(poly_group_lib().hpccg_hip_group_poly_last_spectrum(hs, P, C.byref(lo), C.byref(hi)),
-           "group_last_spectrum_poly")
-    return lo.value, hi.value
+    return _group_last_spectrum("group_last_spectrum_poly", poly_group_lib().hpccg_hip_group_poly_last_spectrum, Ms)
 
 
 def group_poly_workspace_bytes(M: Matrix) -> int:
@@ -1495,9 +1467,6 @@ def group_poly_live_workspaces() -> int:
 # ---------------------------------------------------------------------------
 # ... with the steps streamed from the members' fp32 images (include/hpccg_hip_poly32_group.h)
 # ---------------------------------------------------------------------------
-_POLY32_HALO_COPIES_ENV = "HPCCG_GROUP_POLY32_HALO_COPIES"
-
-
 def group_HPCCG_poly32(Ms: list, Bs, Xs, degree: int = 2, lmin=None, lmax=None, minvs=None, max_iter: int = 500,
                        tolerance: float = 0.0, nrhs=None, ldb=None, ldx=None, halo_copies: bool = False):
     """group_HPCCG_poly with every member's polynomial steps streamed from an
@@ -1506,40 +1475,16 @@ def group_HPCCG_poly32(Ms: list, Bs, Xs, degree: int = 2, lmin=None, lmax=None, 
     (group_poly32_info) every column is group_HPCCG_poly bit for bit; degree 0 is
     group_HPCCG_pcg bit for bit on any matrix; a group of one is HPCCG_poly32 bit
     for bit. The arguments and the result are group_HPCCG_poly's."""
-    L = poly32_group_lib()
-    P = len(Ms)
-    if len(Bs) != P or len(Xs) != P:
-        raise HPCCGError(f"{P} members, {len(Bs)} B and {len(Xs)} X column sets")
-    hs = (C.c_void_p * P)(*[M.h for M in Ms])
-    bp, nb, ldb_ = _group_cols(Bs, nrhs, ldb, "Bs")
-    xp, nx_, ldx_ = _group_cols(Xs, nrhs, ldx, "Xs")
-    if nb != nx_:
-        raise HPCCGError(f"Bs holds {nb} columns, Xs {nx_}")
-    mp = _group_minvs(Ms, minvs)
-    it = np.zeros(max(nb, 1), np.int32)
-    nr = np.zeros(max(nb, 1), np.float64)
-    times = np.zeros(7, np.float64)
-    with _halo_copies_env(halo_copies, _POLY32_HALO_COPIES_ENV):
-        rc = L.hpccg_hip_group_poly32_solve_device(hs, P, nb, bp, ldb_, xp, ldx_, mp, int(degree),
-                                                   0.0 if lmin is None else float(lmin),
-                                                   0.0 if lmax is None else float(lmax), max_iter, tolerance,
-                                                   it.ctypes.data_as(C.POINTER(C.c_int)),
-                                                   nr.ctypes.data_as(C.POINTER(C.c_double)),
-                                                   times.ctypes.data_as(C.POINTER(C.c_double)))
-    _check(rc, "group_HPCCG_poly32")
-    return it[:nb], nr[:nb], times
+    return _group_solve("group_HPCCG_poly32", poly32_group_lib().hpccg_hip_group_poly32_solve_device,
+                        "HPCCG_GROUP_POLY32_HALO_COPIES", Ms, Bs, Xs, minvs, nrhs, ldb, ldx, halo_copies,
+                        *_interval(degree, lmin, lmax), max_iter, tolerance)
 
 
 def group_poly32_bound(Ms: list, minvs=None) -> float:
     """The symmetric Gershgorin bound of the group's global fp64 matrix that
     group_HPCCG_poly32 takes for lmax (group_poly_bound's value); minvs: per
     member a device tensor / pointer of its nrow entries, or None for Jacobi."""
-    P = len(Ms)
-    hs = (C.c_void_p * P)(*[M.h for M in Ms])
-    v = C.c_double(0.0)
-    _check(poly32_group_lib().hpccg_hip_group_poly32_bound(hs, P, _group_minvs(Ms, minvs), C.byref(v)),
-           "group_poly32_bound")
-    return v.value
+    return _group_bound("group_poly32_bound", poly32_group_lib().hpccg_hip_group_poly32_bound, Ms, minvs)
 
 
 def group_poly32_info(Ms: list) -> list:
@@ -1547,7 +1492,7 @@ def group_poly32_info(Ms: list) -> list:
     use), one dict per member: exact (every value of the member's rows survives
     double -> float -> double), image_bytes, inexact_values."""
     P = len(Ms)
-    hs = (C.c_void_p * P)(*[M.h for M in Ms])
+    hs = _handles(Ms)
     a = (C.c_longlong * (4 * P))()
     _check(poly32_group_lib().hpccg_hip_group_poly32_info(hs, P, a), "group_poly32_info")
     return [{"exact": int(a[4 * r]),"image_bytes": int(a[4 * r + 1]), "inexact_values": int(a[4 * r + 2])}
@@ -1556,24 +1501,14 @@ def group_poly32_info(Ms: list) -> list:
 
 def group_last_trace_poly32(Ms: list, col: int, cap: int = 100000) -> np.ndarray:
     """Residual trace (norm of r) of column col of the last group_HPCCG_poly32 on Ms."""
-    P = len(Ms)
-    hs = (C.c_void_p * P)(*[M.h for M in Ms])
-    out = np.zeros(cap, np.float64)
-    n = poly32_group_lib().hpccg_hip_group_poly32_last_trace(hs, P, int(col),
-                                                             out.ctypes.data_as(C.POINTER(C.c_double)), cap)
-    if n < 0:
-        _check(n, "group_last_trace_poly32")
-    return out[:n]
+    return _group_last_trace("group_last_trace_poly32", poly32_group_lib().hpccg_hip_group_poly32_last_trace, Ms, col,
+                             cap)
 
 
 def group_last_spectrum_poly32(Ms: list) -> tuple:
     """(lmin, lmax) the last group_HPCCG_poly32 on Ms used."""
-    P = len(Ms)
-    hs = (C.c_void_p * P)(*[M.h for M in Ms])
-    lo, hi = C.c_double(0.0), C.c_double(0.0)
-    _check(poly32_group_lib().hpccg_hip_group_poly32_last_spectrum(hs, P, C.byref(lo), C.byref(hi)),
-           "group_last_spectrum_poly32")
-    return lo.value, hi.value
+    return _group_last_spectrum("group_last_spectrum_poly32", poly32_group_lib().hpccg_hip_group_poly32_last_spectrum,
+                                Ms)
 
 
 def group_poly32_workspace_bytes(M: Matrix) -> int:
@@ -1594,9 +1529,6 @@ def group_poly32_live_workspaces() -> int:
 # ---------------------------------------------------------------------------
 # single-reduction preconditioned solve over an in-process group (include/hpccg_hip_srcg_group.h)
 # ---------------------------------------------------------------------------
-_SRCG_HALO_COPIES_ENV = "HPCCG_GROUP_SRCG_HALO_COPIES"
-
-
 def group_HPCCG_srcg(Ms: list, Bs, Xs, max_iter: int = 500, tolerance: float = 0.0, minvs=None, nrhs=None, ldb=None,
                      ldx=None, halo_copies: bool = False):
     """nrhs single-reduction preconditioned CG solves over an in-process group
@@ -1607,38 +1539,14 @@ def group_HPCCG_srcg(Ms: list, Bs, Xs, max_iter: int = 500, tolerance: float = 0
     updated in place. halo_copies (diagnostic): move the ghost planes of u by
     one copy per column and side instead of one kernel launch per member; the
     bits are the same. Returns (niters[nrhs], normr[nrhs], times)."""
-    L = srcg_group_lib()
-    P = len(Ms)
-    if len(Bs) != P or len(Xs) != P:
-        raise HPCCGError(f"{P} members, {len(Bs)} B and {len(Xs)} X column sets")
-    hs = (C.c_void_p * P)(*[M.h for M in Ms])
-    bp, nb, ldb_ = _group_cols(Bs, nrhs, ldb, "Bs")
-    xp, nx_, ldx_ = _group_cols(Xs, nrhs, ldx, "Xs")
-    if nb != nx_:
-        raise HPCCGError(f"Bs holds {nb} columns, Xs {nx_}")
-    mp = _group_minvs(Ms, minvs)
-    it = np.zeros(max(nb, 1), np.int32)
-    nr = np.zeros(max(nb, 1), np.float64)
-    times = np.zeros(7, np.float64)
-    with _halo_copies_env(halo_copies, _SRCG_HALO_COPIES_ENV):
-        rc = L.hpccg_hip_group_srcg_solve_device(hs, P, nb, bp, ldb_, xp, ldx_, mp, max_iter, tolerance,
-                                                 it.ctypes.data_as(C.POINTER(C.c_int)),
-                                                 nr.ctypes.data_as(C.POINTER(C.c_double)),
-                                                 times.ctypes.data_as(C.POINTER(C.c_double)))
-    _check(rc, "group_HPCCG_srcg")
-    return it[:nb], nr[:nb], times
+    return _group_solve("group_HPCCG_srcg", srcg_group_lib().hpccg_hip_group_srcg_solve_device,
+                        "HPCCG_GROUP_SRCG_HALO_COPIES", Ms, Bs, Xs, minvs, nrhs, ldb, ldx, halo_copies, max_iter,
+                        tolerance)
 
 
 def group_last_trace_srcg(Ms: list, col: int, cap: int = 100000) -> np.ndarray:
     """Residual trace (norm of r) of column col of the last group_HPCCG_srcg on Ms."""
-    P = len(Ms)
-    hs = (C.c_void_p * P)(*[M.h for M in Ms])
-    out = np.zeros(cap, np.float64)
-    n = srcg_group_lib().hpccg_hip_group_srcg_last_trace(hs, P, int(col), out.ctypes.data_as(C.POINTER(C.c_double)),
-                                                         cap)
-    if n < 0:
-        _check(n, "group_last_trace_srcg")
-    return out[:n]
+    return _group_last_trace("group_last_trace_srcg", srcg_group_lib().hpccg_hip_group_srcg_last_trace, Ms, col, cap)
 
 
 def group_srcg_workspace_bytes(M: Matrix) -> int:

@@ -480,10 +480,7 @@ int hpccg_hip_group_batch_solve_device(hpccg_hip_matrix* const* Ms, int nranks, 
                                        double tolerance, int* niters, double* normr, double* times)
 {
     TRY(check_group_args(kGroupWho, Ms, nranks));
-    if (nrhs <= 0) return fail(HPCCG_HIP_EINVAL, "group batch: nrhs %d (at least 1)", nrhs);
-    if (max_iter < 0) return fail(HPCCG_HIP_EINVAL, "group batch: max_iter %d is negative", max_iter);
-    if (!B_dev || !ldb || !X_dev || !ldx || !niters || !normr)
-        return fail(HPCCG_HIP_EINVAL, "group batch: NULL argument (B_dev, ldb, X_dev, ldx, niters or normr)");
+    TRY(check_group_columns(kGroupWho, nrhs, max_iter, B_dev, ldb, X_dev, ldx, niters, normr));
     for (int r = 0; r < nranks; r++)
         if (!B_dev[r] || !X_dev[r]) return fail(HPCCG_HIP_EINVAL, "group batch: B_dev[%d] or X_dev[%d] is NULL", r, r);
     BatchGroup G;

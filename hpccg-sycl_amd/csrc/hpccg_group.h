@@ -1,6 +1,6 @@
 // hpccg_group.h -- the column recurrence of hpccg_columns.h over an in-process
 // rank group, shared by the group solvers (hpccg_batch.hip, hpccg_pcg_group.hip,
-// hpccg_poly_group.hip, hpccg_poly32_group.hip).
+// hpccg_srcg_group.hip, hpccg_poly_group.hip, hpccg_poly32_group.hip).
 // Member r is rank r of a z-slab job: it runs its unit's kernels on its own
 // rows, on its own stream, in a workspace of its own; the ghost planes of every
 // column's p move between the members after the p update, each member's
@@ -167,6 +167,17 @@ int check_group_args(const char* who, hpccg_hip_matrix* const* Ms, int nranks)
     if (!Ms) return fail(HPCCG_HIP_EINVAL, "%s: Ms is NULL", who);
     if (nranks < 1 || nranks > kMaxMembers)
         return fail(HPCCG_HIP_EINVAL, "%s: nranks %d (1 to %d members)", who, nranks, kMaxMembers);
+    return 0;
+}
+
+// What every unit's solve_device checks next: the counts, then the arrays as such.
+int check_group_columns(const char* who, int nrhs, int max_iter, const void* B_dev, const void* ldb, const void* X_dev,
+                        const void* ldx, const void* niters, const void* normr)
+{
+    if (nrhs <= 0) return fail(HPCCG_HIP_EINVAL, "%s: nrhs %d (at least 1)", who, nrhs);
+    if (max_iter < 0) return fail(HPCCG_HIP_EINVAL, "%s: max_iter %d is negative", who, max_iter);
+    if (!B_dev || !ldb || !X_dev || !ldx || !niters || !normr)
+        return fail(HPCCG_HIP_EINVAL, "%s: NULL argument (B_dev, ldb, X_dev, ldx, niters or normr)", who);
     return 0;
 }
 
@@ -370,12 +381,11 @@ int group_sum(const Group<W, A>& G, const GroupTotals& gt, int which, const Grou
     return 0;
 }
 
-// The unit's CG over the group on the columns staged in the members' b and x:
-// run_recurrence's launch sequence on every member's stream, the halo after
-// every p update and the group's sum after every finalize.
+// The frame of a unit's launch loop over the group (group_run_cg below,
+// group_run_srcg in hpccg_srcg_group.hip).
+// What the sum kernel reads and stores on the members.
 template <class W, class A>
-int group_run_cg(const Group<W, A>& G, int nrhs, int max_iter, double tol, const GroupLaunch<W, A>& L, int* niters,
-                 double* normr, double* wall)
+GroupTotals group_totals(const Group<W, A>& G)
 {
     GroupTotals gt{};
     gt.nranks = G.P;
@@ -384,9 +394,48 @@ int group_run_cg(const Group<W, A>& G, int nrhs, int max_iter, double tol, const
         gt.tot[r] = G.w[r]->tot;
         gt.st[r] = G.w[r]->st;
     }
+    return gt;
+}
+
+// Every kCheckEvery iterations the host reads member 0's "columns ended" word
+// (the sum kernel keeps it): ended once every column is frozen on every member.
+template <class W, class A>
+int group_ended(const Group<W, A>& G, int nrhs, bool* ended)
+{
     W* w0 = G.w[0];
+    HIP_TRY(hipGetLastError());
     TRY(use(G, 0));
-    HIP_TRY(hipEventRecord(w0->ev0, G.v[0].stream));
+    HIP_TRY(hipMemcpyAsync(w0->h_ended, w0->ended, sizeof(int), hipMemcpyDeviceToHost, G.v[0].stream));
+    HIP_TRY(hipStreamSynchronize(G.v[0].stream));
+    *ended = *w0->h_ended >= nrhs;
+    return 0;
+}
+
+// The end of the solve on member 0's stream, whose last launch followed every
+// member's; then the other members' streams run dry.
+template <class W, class A>
+int group_finish(const Group<W, A>& G, int nrhs, int* niters, double* normr, double* wall)
+{
+    HIP_TRY(hipGetLastError());
+    TRY(use(G, 0));
+    TRY(finish_recurrence(G.w[0], nrhs, niters, normr, wall));
+    for (int r = 1; r < G.P; r++) {  // (the last sum's event was their streams' last wait)
+        TRY(use(G, r));
+        HIP_TRY(hipStreamSynchronize(G.v[r].stream));
+    }
+    return 0;
+}
+
+// The unit's CG over the group on the columns staged in the members' b and x:
+// run_recurrence's launch sequence on every member's stream, the halo after
+// every p update and the group's sum after every finalize.
+template <class W, class A>
+int group_run_cg(const Group<W, A>& G, int nrhs, int max_iter, double tol, const GroupLaunch<W, A>& L, int* niters,
+                 double* normr, double* wall)
+{
+    const GroupTotals gt = group_totals(G);
+    TRY(use(G, 0));
+    HIP_TRY(hipEventRecord(G.w[0]->ev0, G.v[0].stream));
     for (int r = 0; r < G.P; r++) {
         TRY(use(G, r));
         L.init(G.w[r], G.a[r], max_iter, tol);
@@ -423,22 +472,12 @@ int group_run_cg(const Group<W, A>& G, int nrhs, int max_iter, double tol, const
         }
         TRY(group_sum(G, gt, kDotRR, L));
         if (k % kCheckEvery == 0 && k + 1 < max_iter) {
-            HIP_TRY(hipGetLastError());
-            TRY(use(G, 0));
-            HIP_TRY(hipMemcpyAsync(w0->h_ended, w0->ended, sizeof(int), hipMemcpyDeviceToHost, G.v[0].stream));
-            HIP_TRY(hipStreamSynchronize(G.v[0].stream));
-            if (*w0->h_ended >= nrhs) break;  // every column is frozen on every member
+            bool ended = false;
+            TRY(group_ended(G, nrhs, &ended));
+            if (ended) break;
         }
     }
-    HIP_TRY(hipGetLastError());
-    // the end on member 0's stream, whose last launch followed every member's
-    TRY(use(G, 0));
-    TRY(finish_recurrence(w0, nrhs, niters, normr, wall));
-    for (int r = 1; r < G.P; r++) {  // (the last sum's event was their streams' last wait)
-        TRY(use(G, r));
-        HIP_TRY(hipStreamSynchronize(G.v[r].stream));
-    }
-    return 0;
+    return group_finish(G, nrhs, niters, normr, wall);
 }
 
 // The callers' B and X (device arrays, one per member) into the members' b and x.

@@ -4,9 +4,9 @@
 // columns and fp64 SpMM form, the matrix check, the diagonal preconditioner
 // with its refusals, the solve (argument checks, the empty matrix, staging B
 // and X, the two `times` slots) and the bodies of the bookkeeping exports.
-// The group units take the dispatch and the bookkeeping bodies
-// (hpccg_pcg_group.hip; hpccg_poly_group.hip and hpccg_poly32_group.hip through
-// hpccg_poly_group_host.h); hpccg_batch.hip and hpccg_mixed.hip, whose launchers
+// The group units take the dispatch and the bookkeeping bodies through
+// hpccg_group_host.h (hpccg_pcg_group.hip, hpccg_srcg_group.hip; hpccg_poly_group.hip
+// and hpccg_poly32_group.hip under hpccg_poly_group_host.h); hpccg_batch.hip and hpccg_mixed.hip, whose launchers
 // and solves are their own, take the matrix check and the bookkeeping bodies.
 // A unit hands over one traits struct U with what it uses of
 //   Args, Workspace       its kernel arguments (a ColArgs) and its workspace (a

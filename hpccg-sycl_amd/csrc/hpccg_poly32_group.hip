@@ -342,7 +342,7 @@ int hpccg_hip_group_poly32_last_spectrum(hpccg_hip_matrix* const* Ms, int nranks
 
 int hpccg_hip_group_poly32_last_trace(hpccg_hip_matrix* const* Ms, int nranks, int col, double* out, int cap)
 {
-    return group_poly_last_trace<GroupPoly32>(Ms, nranks, col, out, cap);
+    return group_last_trace<GroupPoly32>(Ms, nranks, col, out, cap);
 }
 
 int hpccg_hip_group_poly32_info(hpccg_hip_matrix* const* Ms, int nranks, long long* out)
@@ -351,7 +351,7 @@ int hpccg_hip_group_poly32_info(hpccg_hip_matrix* const* Ms, int nranks, long lo
     if (!out) return fail(HPCCG_HIP_EINVAL, "group poly32: out is NULL");
     for (int r = 0; r < nranks; r++)
         if (!Ms[r]) return fail(HPCCG_HIP_EINVAL, "group poly32: Ms[%d] is NULL", r);  // (before any is looked at)
-    PolyGroupOf<GroupPoly32> G;
+    GroupOf<GroupPoly32> G;
     TRY(check_group(GroupPoly32::who, Ms, nranks, kOneForwarded, &G));
     return keep_device([&]() -> int {
         for (int r = 0; r < nranks; r++) {

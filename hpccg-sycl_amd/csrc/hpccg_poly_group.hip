@@ -33,9 +33,11 @@
 // interval are hpccg_poly_host.h, shared with hpccg_poly.hip and
 // hpccg_poly32.hip; the dispatch of a launch on a chunk's columns and SpMM form
 // and the bookkeeping exports are hpccg_onerank_host.h, shared with
-// hpccg_pcg.hip and the rest; the members' preconditioner and bound, the update phase
-// with the halos of z (group_poly_update: the ordering argument is written
-// there) and the solve are hpccg_poly_group_host.h, shared with
+// hpccg_pcg.hip and the rest; the members' preconditioner, the argument checks
+// and the staging of a group solve are hpccg_group_host.h, shared with
+// hpccg_pcg_group.hip and hpccg_srcg_group.hip; the members' bound, the update
+// phase with the halos of z (group_poly_update: the ordering argument is
+// written there) and the solve are hpccg_poly_group_host.h, shared with
 // hpccg_poly32_group.hip. This unit keeps its kernels and its traits. Ordering
 // between the members is by stream events only. No kernel here waits on another
 // block.
@@ -232,7 +234,7 @@ int hpccg_hip_group_poly_last_spectrum(hpccg_hip_matrix* const* Ms, int nranks, 
 
 int hpccg_hip_group_poly_last_trace(hpccg_hip_matrix* const* Ms, int nranks, int col, double* out, int cap)
 {
-    return group_poly_last_trace<GroupPoly>(Ms, nranks, col, out, cap);
+    return group_last_trace<GroupPoly>(Ms, nranks, col, out, cap);
 }
 
 int hpccg_hip_group_poly_release(hpccg_hip_matrix* M) { return unit_release<GroupPoly>(M); }

@@ -1,21 +1,19 @@
 // hpccg_poly_group_host.h -- the host code of the Chebyshev polynomial
 // preconditioned CG over an in-process rank group, shared by the polynomial
-// group units (hpccg_poly_group.hip, hpccg_poly32_group.hip): the members'
-// preconditioner and bound, the group's update phase with the halos of z
-// (group_poly_update: the ordering argument is written there), the solve and
-// the bodies of the units' extern "C" functions that take the group (release,
-// workspace_bytes and live_workspaces are hpccg_onerank_host.h's). It stands on
-// hpccg_group.h (the group engine), hpccg_poly_host.h (the polynomial's
-// workspace, arguments, launchers and interval) and, through it,
-// hpccg_onerank_host.h (the launch dispatch, the init, SpMM and finalize
-// launchers).
-// A unit hands over one traits struct U: what those two headers' launchers
-// need (Args, Workspace, row0, init, p, update, finalize, spmm_a, spmm_sell,
-// and step, step_sell where it runs the fp64 steps) and further
-//   who                   the name in front of its messages ("group poly")
-//   halo_env              the environment variable of the halo by copies
-//   sum, halo             its group sum and halo kernels
-//   diag, check, q, bound, bound_top   the preconditioner's and the bound's kernels
+// group units (hpccg_poly_group.hip, hpccg_poly32_group.hip): what is
+// polynomial in them -- the members' bound, the group's update phase with the
+// halos of z (group_poly_update: the ordering argument is written there), the
+// interval of a solve and the bodies of solve_device, bound and last_spectrum.
+// It stands on hpccg_group_host.h (the members' preconditioner, the argument
+// checks and the staging of a group solve, last_trace; through it
+// hpccg_group.h, the group engine, and hpccg_onerank_host.h, the launch
+// dispatch and the bookkeeping bodies) and hpccg_poly_host.h (the polynomial's
+// workspace, arguments, launchers and interval).
+// A unit hands over one traits struct U: what those headers ask for (Args,
+// Workspace, who, halo_env, sum, halo, diag, check; row0, init, p, update,
+// finalize, spmm_a, spmm_sell, and step, step_sell where it runs the fp64
+// steps) and further
+//   q, bound, bound_top   the bound's kernels
 //   launch_spmm(w, a, prologue), launch_step(w, a)   a member's SpMM and one
 //                         step over the chunks of columns
 //   image(w, r)           what the unit builds per member before the
@@ -25,83 +23,24 @@
 // The __global__ entry points and the extern "C" definitions stay in the units.
 // Internal linkage (each unit compiles its own copy), like hpccg_columns.h.
 #pragma once
-#include <cstdlib>
-#include <vector>
-
-#include "hpccg_group.h"
+#include "hpccg_group_host.h"
 #include "hpccg_poly_host.h"
 
 namespace hpccg {
 
 namespace {
 
+// hpccg_group_host.h's preparation of the members with what a polynomial unit
+// adds: its image before the preconditioner, and beside the member's cache
+// the bound's vectors.
 template <class U>
-using PolyGroupOf = Group<typename U::Workspace, typename U::Args>;
-
-// a group of one is checked and run like any other: nothing forwards it
-constexpr bool kOneForwarded = false;
-
-// The member's cache (hpccg_jacobi.h), its two events and the bound's vectors.
-template <class U>
-int ensure_rest(typename U::Workspace* w)
-{
-    HIP_TRY(hipSetDevice(w->v.device));
-    TRY(w->create_events());
-    TRY(ensure_cache(w));
-    w->p0 = guarded_p_column(w->v).p0;
-    return ensure_bound_vectors(w, guarded_p_column(w->v).pcs);
-}
-
-template <class U>
-int ensure_member_jacobi(typename U::Workspace* w, int r)
-{
-    int row = -1;
-    TRY(build_jacobi(w, U::diag, &row));
-    if (row >= 0)
-        return fail(HPCCG_HIP_EINVAL,
-                    "%s: Jacobi needs a finite diagonal > 0 in every row; on member %d row %d (local) is the "
-                    "first whose diagonal is missing, not finite or <= 0",
-                    U::who, r, row);
-    return 0;
-}
-
-template <class U>
-int stage_member_minv(typename U::Workspace* w, int r, const double* minv)
-{
-    int row = -1;
-    TRY(load_minv(w, minv, hipMemcpyDeviceToDevice, U::check, &row));
-    if (row >= 0)
-        return fail(HPCCG_HIP_EINVAL, "%s: member %d's minv[%d] is not finite and > 0 (the first such entry)", U::who, r,
-                    row);
-    return 0;
-}
-
-template <class U>
-void launch_halo(hipStream_t s, dim3 grid, const HaloArgs& h)
-{
-    hipLaunchKernelGGL(U::halo, grid, dim3(kHaloThreads), 0, s, h);
-}
-
-// The members' records, what the unit builds per member, events, caches and
-// preconditioner vectors: m[r] is member r's padded device m (its muser, or its
-// cached 1 / a_ii).
-template <class U>
-int group_preconditioner(hpccg_hip_matrix* const* Ms, PolyGroupOf<U>* G, const double* const* minv,
+int group_preconditioner(hpccg_hip_matrix* const* Ms, GroupOf<U>* G, const double* const* minv,
                          std::vector<const double*>* m)
 {
-    G->w.assign(G->P, nullptr);
-    m->assign(G->P, nullptr);
-    for (int r = 0; r < G->P; r++) {
-        TRY(g_ws<typename U::Workspace>.record(Ms[r], G->v[r], &G->w[r]));
-        TRY(U::image(G->w[r], r));
-        TRY(ensure_rest<U>(G->w[r]));
-        if (minv)
-            TRY(stage_member_minv<U>(G->w[r], r, minv[r]));
-        else
-            TRY(ensure_member_jacobi<U>(G->w[r], r));
-        (*m)[r] = minv ? G->w[r]->muser : G->w[r]->jac;
-    }
-    return 0;
+    return group_members<U>(Ms, G, minv, m, U::image, [](typename U::Workspace* w) {
+        w->p0 = guarded_p_column(w->v).p0;
+        return ensure_bound_vectors(w, guarded_p_column(w->v).pcs);
+    });
 }
 
 // The symmetric Gershgorin bound of the global matrix with the members' m:
@@ -111,7 +50,7 @@ int group_preconditioner(hpccg_hip_matrix* const* Ms, PolyGroupOf<U>* G, const d
 // the group's bound is the maximum of the members': order-free and exact. A NaN
 // stays one and is refused here. part[r] (may be null): member r's maximum.
 template <class U>
-int compute_group_bound(const PolyGroupOf<U>& G, const std::vector<const double*>& m, bool copies, double* part,
+int compute_group_bound(const GroupOf<U>& G, const std::vector<const double*>& m, HaloLaunch halo, double* part,
                         double* lmax)
 {
     using W = typename U::Workspace;
@@ -124,7 +63,7 @@ int compute_group_bound(const PolyGroupOf<U>& G, const std::vector<const double*
     HIP_TRY(hipGetLastError());
     // (q is written once per call and read by the bound pass only, which every
     // member's stream has finished before this function returns)
-    TRY(group_halo_of(G, 1, copies ? nullptr : launch_halo<U>, [&](int r) {
+    TRY(group_halo_of(G, 1, halo, [&](int r) {
         return HaloBuf{G.w[r]->qbuf + G.w[r]->p0, guarded_p_column(G.v[r]).pcs};
     }));
     for (int r = 0; r < G.P; r++) {
@@ -159,14 +98,14 @@ int compute_group_bound(const PolyGroupOf<U>& G, const std::vector<const double*
 // Jacobi's bound: every member's part is cached in its workspace beside its
 // 1 / a_ii (matrices and groups are immutable); the maximum is retaken per call.
 template <class U>
-int jacobi_group_bound(const PolyGroupOf<U>& G, const std::vector<const double*>& m, bool copies, double* lmax)
+int jacobi_group_bound(const GroupOf<U>& G, const std::vector<const double*>& m, HaloLaunch halo, double* lmax)
 {
     bool built = true;
     for (int r = 0; r < G.P; r++) built = built && G.w[r]->jac_lmax_built;
     if (!built) {
         std::vector<double> part(G.P, 0.0);
         double top = 0.0;
-        TRY(compute_group_bound<U>(G, m, copies, part.data(), &top));
+        TRY(compute_group_bound<U>(G, m, halo, part.data(), &top));
         for (int r = 0; r < G.P; r++) {
             G.w[r]->jac_lmax = part[r];
             G.w[r]->jac_lmax_built = true;
@@ -210,7 +149,7 @@ int jacobi_group_bound(const PolyGroupOf<U>& G, const std::vector<const double*>
 // enter the argument: z and its planes are fp64 vectors in either unit.
 // ---------------------------------------------------------------------------
 template <class U>
-int group_poly_update(const PolyGroupOf<U>& G, int nrhs, bool prologue, HaloLaunch halo)
+int group_poly_update(const GroupOf<U>& G, int nrhs, bool prologue, HaloLaunch halo)
 {
     for (int r = 0; r < G.P; r++) {
         TRY(use(G, r));
@@ -228,99 +167,57 @@ int group_poly_update(const PolyGroupOf<U>& G, int nrhs, bool prologue, HaloLaun
     return 0;
 }
 
-template <class U>
-void launch_group_sum(const typename U::Workspace* w, const typename U::Args& a, const GroupTotals& gt, int which)
-{
-    hipLaunchKernelGGL(U::sum, dim3((a.nrhs + 63) / 64), dim3(64), 0, w->v.stream, a, gt, which);
-}
-
-// copies: the halos by copies (the fallback and the baseline), else by the unit's halo kernel.
-template <class U>
-int group_solve(hpccg_hip_matrix* const* Ms, const PolyGroupOf<U>& G0, int nrhs, const double* const* B,
-                const long long* ldb, double* const* X, const long long* ldx, const double* const* minv, int degree,
-                double lmin, double lmax, int max_iter, double tol, bool copies, int* niters, double* normr,
-                double* times)
-{
-    using W = typename U::Workspace;
-    using A = typename U::Args;
-    PolyGroupOf<U> G = G0;
-    if (times) std::fill(times, times + 7, 0.0);
-    if (max_iter < 1) max_iter = 1;
-    G.a.resize(G.P);
-    // the preconditioner and the interval first, on every member: a refused
-    // call leaves every X as it is
-    std::vector<const double*> m;
-    TRY(group_preconditioner<U>(Ms, &G, minv, &m));
-    double cheb0 = 0.0, aj[kPolyMaxDegree + 1] = {}, bj[kPolyMaxDegree + 1] = {};
-    TRY(resolve_interval(U::who, degree, &lmin, &lmax, &cheb0, aj, bj, [&](double* top) {
-        return minv ? compute_group_bound<U>(G, m, copies, nullptr, top) : jacobi_group_bound<U>(G, m, copies, top);
-    }));
-    for (int r = 0; r < G.P; r++) {
-        W* w = G.w[r];
-        TRY(ensure_vectors(w, nrhs, max_iter, guarded_p_column(w->v).pcs, 3));
-        w->degree = degree;
-        w->cheb0 = cheb0;
-        std::copy(aj, aj + kPolyMaxDegree + 1, w->aj);
-        std::copy(bj, bj + kPolyMaxDegree + 1, w->bj);
-        G.a[r] = make_args<U>(w, nrhs, m[r]);
-    }
-    G.w[0]->last_lmin = lmin;
-    G.w[0]->last_lmax = lmax;
-    G.w[0]->solved = true;
-    TRY(group_stage_in(G, nrhs, B, ldb, X, ldx));
-    const GroupLaunch<W, A> launch = {launch_init<U>,
-                                      launch_p<U>,
-                                      U::launch_spmm,
-                                      launch_update0<U>,
-                                      launch_finalize<U>,
-                                      launch_group_sum<U>,
-                                      copies ? nullptr : launch_halo<U>,
-                                      group_poly_update<U>};
-    double wall = 0.0;
-    TRY(group_run_cg(G, nrhs, max_iter, tol, launch, niters, normr, &wall));
-    TRY(group_stage_out(G, nrhs, X, ldx));
-    if (times) times[0] = wall;
-    return 0;
-}
-
-template <class U>
-bool halo_by_copies()
-{
-    // diagnostics: the halos by copies, the A/B of the unit's halo kernel (the group benchmark tools)
-    return std::getenv(U::halo_env) != nullptr;
-}
-
 // ---------------------------------------------------------------------------
 // The bodies of a unit's extern "C" functions
 // ---------------------------------------------------------------------------
+// hpccg_group_host.h's solve_device with the degree and the bounds checked
+// after the arrays, and the interval resolved once every member's m is in hand.
 template <class U>
 int group_poly_solve_device(hpccg_hip_matrix* const* Ms, int nranks, int nrhs, const double* const* B_dev,
                             const long long* ldb, double* const* X_dev, const long long* ldx,
                             const double* const* minv_dev, int degree, double lmin, double lmax, int max_iter,
                             double tolerance, int* niters, double* normr, double* times)
 {
+    using W = typename U::Workspace;
     const char* who = U::who;
-    TRY(check_group_args(who, Ms, nranks));
-    if (nrhs <= 0) return fail(HPCCG_HIP_EINVAL, "%s: nrhs %d (at least 1)", who, nrhs);
-    if (max_iter < 0) return fail(HPCCG_HIP_EINVAL, "%s: max_iter %d is negative", who, max_iter);
-    if (!B_dev || !ldb || !X_dev || !ldx || !niters || !normr)
-        return fail(HPCCG_HIP_EINVAL, "%s: NULL argument (B_dev, ldb, X_dev, ldx, niters or normr)", who);
-    for (int r = 0; r < nranks; r++) {
-        if (!Ms[r]) return fail(HPCCG_HIP_EINVAL, "%s: Ms[%d] is NULL", who, r);  // (before any is looked at)
-        if (!B_dev[r] || !X_dev[r]) return fail(HPCCG_HIP_EINVAL, "%s: B_dev[%d] or X_dev[%d] is NULL", who, r, r);
-        if (minv_dev && !minv_dev[r]) return fail(HPCCG_HIP_EINVAL, "%s: minv_dev[%d] is NULL", who, r);
-    }
-    if (degree < 0 || degree > kPolyMaxDegree)
-        return fail(HPCCG_HIP_EINVAL, "%s: degree %d (0 to %d)", who, degree, kPolyMaxDegree);
-    TRY(check_bounds(who, lmin, lmax));
-    PolyGroupOf<U> G;
-    TRY(check_group(who, Ms, nranks, kOneForwarded, &G));
-    TRY(check_group_lds(who, G, ldb, ldx, "ldb, ldx"));
-    const bool copies = halo_by_copies<U>();
-    return keep_device([&] {
-        return group_solve<U>(Ms, G, nrhs, B_dev, ldb, X_dev, ldx, minv_dev, degree, lmin, lmax, max_iter, tolerance,
-                              copies, niters, normr, times);
-    });
+    return group_solve_device<U>(
+        Ms, nranks, nrhs, B_dev, ldb, X_dev, ldx, minv_dev, max_iter, niters, normr, times, true,
+        [&]() -> int {
+            if (degree < 0 || degree > kPolyMaxDegree)
+                return fail(HPCCG_HIP_EINVAL, "%s: degree %d (0 to %d)", who, degree, kPolyMaxDegree);
+            return check_bounds(who, lmin, lmax);
+        },
+        [&](GroupOf<U>& G, int kmax) -> int {
+            const HaloLaunch halo = halo_launcher<U>();
+            // the preconditioner and the interval first, on every member: a
+            // refused call leaves every X as it is
+            std::vector<const double*> m;
+            TRY(group_preconditioner<U>(Ms, &G, minv_dev, &m));
+            double cheb0 = 0.0, aj[kPolyMaxDegree + 1] = {}, bj[kPolyMaxDegree + 1] = {};
+            TRY(resolve_interval(who, degree, &lmin, &lmax, &cheb0, aj, bj, [&](double* top) {
+                return minv_dev ? compute_group_bound<U>(G, m, halo, nullptr, top)
+                                : jacobi_group_bound<U>(G, m, halo, top);
+            }));
+            for (int r = 0; r < G.P; r++) {
+                W* w = G.w[r];
+                TRY(ensure_vectors(w, nrhs, kmax, guarded_p_column(w->v).pcs, 3));
+                w->degree = degree;
+                w->cheb0 = cheb0;
+                std::copy(aj, aj + kPolyMaxDegree + 1, w->aj);
+                std::copy(bj, bj + kPolyMaxDegree + 1, w->bj);
+                G.a[r] = make_args<U>(w, nrhs, m[r]);
+            }
+            G.w[0]->last_lmin = lmin;
+            G.w[0]->last_lmax = lmax;
+            G.w[0]->solved = true;
+            const GroupLaunch<W, typename U::Args> launch = {launch_init<U>,      launch_p<U>,
+                                                             U::launch_spmm,      launch_update0<U>,
+                                                             launch_finalize<U>,  launch_group_sum<U>,
+                                                             halo,                group_poly_update<U>};
+            return group_run_staged(G, nrhs, B_dev, ldb, X_dev, ldx, times, [&](double* wall) {
+                return group_run_cg(G, nrhs, kmax, tolerance, launch, niters, normr, wall);
+            });
+        });
 }
 
 template <class U>
@@ -331,14 +228,13 @@ int group_poly_bound(hpccg_hip_matrix* const* Ms, int nranks, const double* cons
     if (!lmax) return fail(HPCCG_HIP_EINVAL, "%s: lmax is NULL", who);
     for (int r = 0; minv_dev && r < nranks; r++)
         if (!minv_dev[r]) return fail(HPCCG_HIP_EINVAL, "%s: minv_dev[%d] is NULL", who, r);
-    PolyGroupOf<U> G;
+    GroupOf<U> G;
     TRY(check_group(who, Ms, nranks, kOneForwarded, &G));
-    const bool copies = halo_by_copies<U>();
+    const HaloLaunch halo = halo_launcher<U>();
     return keep_device([&]() -> int {
         std::vector<const double*> m;
         TRY(group_preconditioner<U>(Ms, &G, minv_dev, &m));
-        return minv_dev ? compute_group_bound<U>(G, m, copies, nullptr, lmax)
-                        : jacobi_group_bound<U>(G, m, copies, lmax);
+        return minv_dev ? compute_group_bound<U>(G, m, halo, nullptr, lmax) : jacobi_group_bound<U>(G, m, halo, lmax);
     });
 }
 
@@ -348,7 +244,7 @@ int group_poly_last_spectrum(hpccg_hip_matrix* const* Ms, int nranks, double* lm
     const char* who = U::who;
     TRY(check_group_args(who, Ms, nranks));
     if (!lmin || !lmax) return fail(HPCCG_HIP_EINVAL, "%s: NULL argument (lmin or lmax)", who);
-    PolyGroupOf<U> G;
+    GroupOf<U> G;
     TRY(check_group(who, Ms, nranks, kOneForwarded, &G));
     // one interval for the group: kept with member 0's record
     const typename U::Workspace* w = g_ws<typename U::Workspace>.find(Ms[0]);
@@ -357,23 +253,6 @@ int group_poly_last_spectrum(hpccg_hip_matrix* const* Ms, int nranks, double* lm
     *lmin = w->last_lmin;
     *lmax = w->last_lmax;
     return 0;
-}
-
-template <class U>
-int group_poly_last_trace(hpccg_hip_matrix* const* Ms, int nranks, int col, double* out, int cap)
-{
-    const char* who = U::who;
-    TRY(check_group_args(who, Ms, nranks));
-    if (!out) return fail(HPCCG_HIP_EINVAL, "%s: out is NULL", who);
-    PolyGroupOf<U> G;
-    TRY(check_group(who, Ms, nranks, kOneForwarded, &G));
-    // one set of all-reduced scalars: kept with member 0's record
-    const typename U::Workspace* w = g_ws<typename U::Workspace>.find(Ms[0]);
-    const int n = copy_trace(w, col, out, cap);
-    if (n < 0)
-        return fail(HPCCG_HIP_EINVAL, "%s: no trace of column %d (the last group solve had %d)", who, col,
-                    w ? (int)w->trace.size() : 0);
-    return n;
 }
 
 }  // namespace

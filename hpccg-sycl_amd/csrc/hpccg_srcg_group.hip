@@ -27,17 +27,15 @@
 // The group and its checks, the guarded u column, the bodies of the halo
 // kernel, the halo, the ordering of the sum and the staging of B and X are
 // hpccg_group.h; the dispatch of a launch on a chunk's columns and SpMM form
-// and the bookkeeping exports are hpccg_onerank_host.h; this unit adds the sum
-// kernel, the members' preconditioner and the launch loop. Ordering between the
-// members is by stream events. No kernel here waits on another block.
+// and the bookkeeping exports are hpccg_onerank_host.h; the member's workspace
+// and preconditioner, the argument checks and the solve are hpccg_group_host.h,
+// shared with hpccg_pcg_group.hip; this unit adds p and s, the sum kernel and
+// the launch loop. Ordering between the members is by stream events. No kernel
+// here waits on another block.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cstdlib>
-
 #include "../../include/hpccg_hip_srcg_group.h"
-#include "hpccg_group.h"
-#include "hpccg_onerank_host.h"
+#include "hpccg_group_host.h"
 #include "hpccg_srcg_bodies.h"
 
 #pragma clang fp contract(off)
@@ -135,109 +133,49 @@ __global__ void k_srcg_group_check(const double* __restrict__ m, int n, int* bad
 // One member's workspace: the columns (u's guarded, with the member's ghost
 // planes), p and s, the cached 1 / a_ii with its verdict and a slot for a
 // caller's m. The member's other workspaces are other records.
-struct Workspace : TraceWorkspace, GroupMember, JacobiCache {
-    double *r = nullptr, *x = nullptr, *b = nullptr;
+struct Workspace : GroupWorkspace {
     double *pd = nullptr, *sd = nullptr;  // p and s = A p (never zeroed again: k == 1 reads u and w)
-
-    Workspace() { ndots = 3; }
 
     void free_own_vectors()
     {
-        for (double* q : {r, x, b, pd, sd})
+        GroupWorkspace::free_own_vectors();
+        for (double* q : {pd, sd})
             if (q) (void)hipFree(q);
-        r = x = b = pd = sd = nullptr;
+        pd = sd = nullptr;
     }
-    void free_own_rest()
-    {
-        free_cache();
-        destroy_events();
-    }
-    long long total_bytes() const { return bytes + rest_bytes; }
 };
 
-// The member's cache (hpccg_jacobi.h) and its two events.
-int ensure_rest(Workspace* w)
-{
-    HIP_TRY(hipSetDevice(w->v.device));
-    TRY(w->create_events());
-    return ensure_cache(w);
-}
-
-// Jacobi on member r: the cached 1.0 / a_ii of its rows, from its own image, or
-// the refusal of a member it does not exist for.
-int ensure_jacobi(Workspace* w, int r)
-{
-    int row = -1;
-    TRY(build_jacobi(w, k_srcg_group_diag, &row));
-    if (row >= 0)
-        return fail(HPCCG_HIP_EINVAL,
-                    "group srcg: Jacobi needs a finite diagonal > 0 in every row; on member %d row %d (local) is the "
-                    "first whose diagonal is missing, not finite or <= 0",
-                    r, row);
-    return 0;
-}
-
-// A call's own m of member r: into the padded muser, every entry finite and > 0.
-int stage_minv(Workspace* w, int r, const double* minv)
-{
-    int row = -1;
-    TRY(load_minv(w, minv, hipMemcpyDeviceToDevice, k_srcg_group_check, &row));
-    if (row >= 0)
-        return fail(HPCCG_HIP_EINVAL, "group srcg: member %d's minv[%d] is not finite and > 0 (the first such entry)", r,
-                    row);
-    return 0;
-}
-
-// Room for ncols columns (u's are guarded, with the ghost planes) and a
-// history of max_iter + 1 entries per column.
-int ensure_vectors(Workspace* w, int ncols, int max_iter)
-{
-    const MatrixView& v = w->v;
-    const size_t npad = (size_t)v.npad;
-    const PColumn pc = guarded_p_column(v);
-    return ensure_columns(w, ncols, max_iter, true, pc.pcs, 3, [&](int cap) {
-        w->p0 = pc.p0;
-        TRY(alloc_zero(w, &w->r, npad * cap));
-        TRY(alloc_zero(w, &w->x, npad * cap));
-        TRY(alloc_zero(w, &w->b, npad * cap));
-        TRY(alloc_zero(w, &w->pd, npad * cap));
-        TRY(alloc_zero(w, &w->sd, npad * cap));
-        return 0;
-    });
-}
-
-SrcgArgs make_args(const Workspace* w, int nrhs, const double* m)
-{
-    const MatrixView& v = w->v;
-    SrcgArgs a{};
-    fill_args(&a, w, nrhs);  // (Ap: w = A u)
-    a.tri = 1;
-    a.p = w->pbuf + w->p0;  // u
-    a.r = w->r;
-    a.rcs = w->vcs;
-    a.x = w->x;
-    a.b = w->b;
-    a.minv = m;
-    a.aval = v.aval;
-    a.vals = v.vals;
-    a.pd = w->pd;
-    a.sd = w->sd;
-    return a;
-}
-
-// hpccg_onerank_host.h's launchers over this unit's kernels
+// hpccg_group_host.h's and hpccg_onerank_host.h's host code over this unit's kernels
 struct SrcgGroupUnit {
     using Args = SrcgArgs;
     using Workspace = hpccg::Workspace;
     static constexpr const char* who = "group srcg";
+    // diagnostics: the halo by copies, the A/B of k_srcg_group_halo (tools/group_srcg_bench.py)
+    static constexpr const char* halo_env = "HPCCG_GROUP_SRCG_HALO_COPIES";
+    static int own_vectors(Workspace* w, size_t count)
+    {
+        TRY(alloc_zero(w, &w->pd, count));
+        return alloc_zero(w, &w->sd, count);
+    }
+    static SrcgArgs make_args(const Workspace* w, int nrhs, const double* m)
+    {
+        SrcgArgs a{};
+        fill_member_args(&a, w, nrhs, m);
+        a.pd = w->pd;
+        a.sd = w->sd;
+        return a;
+    }
 
     static constexpr auto init = k_srcg_group_init;
     template <int kW, int kR, int kWaves>
     static constexpr auto spmm_a = k_srcg_group_spmm_a<kW, kR, kWaves>;
     template <int kR>
     static constexpr auto spmm_sell = k_srcg_group_spmm_sell<kR>;
+    static constexpr auto halo = k_srcg_group_halo;
+    static constexpr auto diag = k_srcg_group_diag;
+    static constexpr auto check = k_srcg_group_check;
 };
-constexpr const char* kGroupWho = SrcgGroupUnit::who;
+using SrcgGroup = GroupOf<SrcgGroupUnit>;
 
 void launch_t(const Workspace* w, const SrcgArgs& a)
 {
@@ -261,15 +199,6 @@ void launch_group_sum(const Workspace* w, const SrcgArgs& a, const GroupTotals& 
 {
     hipLaunchKernelGGL(k_srcg_group_sum, dim3((a.nrhs + 63) / 64), dim3(64), 0, w->v.stream, a, gt);
 }
-
-void launch_halo(hipStream_t s, dim3 grid, const HaloArgs& h)
-{
-    hipLaunchKernelGGL(k_srcg_group_halo, grid, dim3(kHaloThreads), 0, s, h);
-}
-
-using SrcgGroup = Group<Workspace, SrcgArgs>;
-// a group of one is checked and run like any other: nothing forwards it
-constexpr bool kOneForwarded = false;
 
 // Every member's stream waits for what its neighbours' streams hold so far.
 // The prologue needs it once: a member's step overwrites the t rows its
@@ -315,18 +244,11 @@ int group_iteration(const SrcgGroup& G, int nrhs, bool prologue, HaloLaunch halo
 int group_run_srcg(const SrcgGroup& G, int nrhs, int max_iter, double tol, HaloLaunch halo, int* niters,
                    double* normr, double* wall)
 {
-    GroupTotals gt{};
-    gt.nranks = G.P;
-    for (int r = 0; r < G.P; r++) {
-        gt.cap[r] = G.w[r]->cap;
-        gt.tot[r] = G.w[r]->tot;
-        gt.st[r] = G.w[r]->st;
-    }
+    const GroupTotals gt = group_totals(G);
     GroupLaunch<Workspace, SrcgArgs> L{};  // (group_sum takes the sum's launcher from it)
     L.sum = launch_group_sum;
-    Workspace* w0 = G.w[0];
     TRY(use(G, 0));
-    HIP_TRY(hipEventRecord(w0->ev0, G.v[0].stream));
+    HIP_TRY(hipEventRecord(G.w[0]->ev0, G.v[0].stream));
     for (int r = 0; r < G.P; r++) {
         TRY(use(G, r));
         launch_init<SrcgGroupUnit>(G.w[r], G.a[r], max_iter, tol);
@@ -343,54 +265,12 @@ int group_run_srcg(const SrcgGroup& G, int nrhs, int max_iter, double tol, HaloL
     for (int k = 1; k < max_iter; k++) {
         TRY(group_iteration(G, nrhs, false, halo, gt, L));
         if (k % kCheckEvery == 0 && k + 1 < max_iter) {
-            HIP_TRY(hipGetLastError());
-            TRY(use(G, 0));
-            HIP_TRY(hipMemcpyAsync(w0->h_ended, w0->ended, sizeof(int), hipMemcpyDeviceToHost, G.v[0].stream));
-            HIP_TRY(hipStreamSynchronize(G.v[0].stream));
-            if (*w0->h_ended >= nrhs) break;  // every column is frozen on every member
+            bool ended = false;
+            TRY(group_ended(G, nrhs, &ended));
+            if (ended) break;
         }
     }
-    HIP_TRY(hipGetLastError());
-    // the end on member 0's stream, whose last launch followed every member's
-    TRY(use(G, 0));
-    TRY(finish_recurrence(w0, nrhs, niters, normr, wall));
-    for (int r = 1; r < G.P; r++) {  // (the last sum's event was their streams' last wait)
-        TRY(use(G, r));
-        HIP_TRY(hipStreamSynchronize(G.v[r].stream));
-    }
-    return 0;
-}
-
-// copies: the halo by copies (the fallback and the baseline), else by k_srcg_group_halo.
-int group_solve(hpccg_hip_matrix* const* Ms, const SrcgGroup& G0, int nrhs, const double* const* B,
-                const long long* ldb, double* const* X, const long long* ldx, const double* const* minv, int max_iter,
-                double tol, bool copies, int* niters, double* normr, double* times)
-{
-    SrcgGroup G = G0;
-    if (times) std::fill(times, times + 7, 0.0);
-    if (max_iter < 1) max_iter = 1;
-    G.w.assign(G.P, nullptr);
-    G.a.resize(G.P);
-    // the preconditioner first, on every member: a refused one leaves every X as it is
-    for (int r = 0; r < G.P; r++) {
-        TRY(g_ws<Workspace>.record(Ms[r], G.v[r], &G.w[r]));
-        TRY(ensure_rest(G.w[r]));
-        if (minv)
-            TRY(stage_minv(G.w[r], r, minv[r]));
-        else
-            TRY(ensure_jacobi(G.w[r], r));
-    }
-    for (int r = 0; r < G.P; r++) {
-        Workspace* w = G.w[r];
-        TRY(ensure_vectors(w, nrhs, max_iter));
-        G.a[r] = make_args(w, nrhs, minv ? w->muser : w->jac);
-    }
-    TRY(group_stage_in(G, nrhs, B, ldb, X, ldx));
-    double wall = 0.0;
-    TRY(group_run_srcg(G, nrhs, max_iter, tol, copies ? nullptr : launch_halo, niters, normr, &wall));
-    TRY(group_stage_out(G, nrhs, X, ldx));
-    if (times) times[0] = wall;
-    return 0;
+    return group_finish(G, nrhs, niters, normr, wall);
 }
 
 }  // namespace
@@ -408,39 +288,13 @@ int hpccg_hip_group_srcg_solve_device(hpccg_hip_matrix* const* Ms, int nranks, i
                                       const double* const* minv_dev, int max_iter, double tolerance, int* niters,
                                       double* normr, double* times)
 {
-    TRY(check_group_args(kGroupWho, Ms, nranks));
-    if (nrhs <= 0) return fail(HPCCG_HIP_EINVAL, "group srcg: nrhs %d (at least 1)", nrhs);
-    if (max_iter < 0) return fail(HPCCG_HIP_EINVAL, "group srcg: max_iter %d is negative", max_iter);
-    if (!B_dev || !ldb || !X_dev || !ldx || !niters || !normr)
-        return fail(HPCCG_HIP_EINVAL, "group srcg: NULL argument (B_dev, ldb, X_dev, ldx, niters or normr)");
-    for (int r = 0; r < nranks; r++) {
-        if (!B_dev[r] || !X_dev[r]) return fail(HPCCG_HIP_EINVAL, "group srcg: B_dev[%d] or X_dev[%d] is NULL", r, r);
-        if (minv_dev && !minv_dev[r]) return fail(HPCCG_HIP_EINVAL, "group srcg: minv_dev[%d] is NULL", r);
-    }
-    SrcgGroup G;
-    TRY(check_group(kGroupWho, Ms, nranks, kOneForwarded, &G));
-    TRY(check_group_lds(kGroupWho, G, ldb, ldx, "ldb, ldx"));
-    // diagnostics: the halo by copies, the A/B of k_srcg_group_halo (tools/group_srcg_bench.py)
-    const bool copies = std::getenv("HPCCG_GROUP_SRCG_HALO_COPIES") != nullptr;
-    return keep_device([&] {
-        return group_solve(Ms, G, nrhs, B_dev, ldb, X_dev, ldx, minv_dev, max_iter, tolerance, copies, niters, normr,
-                           times);
-    });
+    return group_diag_solve_device<SrcgGroupUnit>(Ms, nranks, nrhs, B_dev, ldb, X_dev, ldx, minv_dev, max_iter,
+                                                  tolerance, niters, normr, times, group_run_srcg);
 }
 
 int hpccg_hip_group_srcg_last_trace(hpccg_hip_matrix* const* Ms, int nranks, int col, double* out, int cap)
 {
-    TRY(check_group_args(kGroupWho, Ms, nranks));
-    if (!out) return fail(HPCCG_HIP_EINVAL, "group srcg: out is NULL");
-    SrcgGroup G;
-    TRY(check_group(kGroupWho, Ms, nranks, kOneForwarded, &G));
-    // one set of all-reduced scalars: kept with member 0's record
-    const Workspace* w = g_ws<Workspace>.find(Ms[0]);
-    const int n = copy_trace(w, col, out, cap);
-    if (n < 0)
-        return fail(HPCCG_HIP_EINVAL, "group srcg: no trace of column %d (the last group solve had %d)", col,
-                    w ? (int)w->trace.size() : 0);
-    return n;
+    return group_last_trace<SrcgGroupUnit>(Ms, nranks, col, out, cap);
 }
 
 int hpccg_hip_group_srcg_release(hpccg_hip_matrix* M) { return unit_release<SrcgGroupUnit>(M); }

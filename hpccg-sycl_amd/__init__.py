@@ -290,6 +290,45 @@ def srcg_group_lib() -> C.CDLL:
     })
 
 
+SRPOLY_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_srpoly.so")
+
+
+def srpoly_lib() -> C.CDLL:
+    """Load libhpccg_hip_srpoly.so (include/hpccg_hip_srpoly.h) on first use. It
+    is linked against libhpccg_hip.so beside it, so lib() is loaded first and
+    both share one copy of the main library."""
+    return _load_unit("srpoly", SRPOLY_LIB_PATH, "the srpoly library", "the single-reduction polynomial solve has no fallback", {
+        "hpccg_hip_srpoly_abi_version": (_ip, []),
+        "hpccg_hip_srpoly_solve_device": (_ip, [_vp, _ip, _vp, _lp, _vp, _lp, _vp, _ip, _dp, _dp, _ip, _dp, _PI, _PD, _PD]),
+        "hpccg_hip_srpoly_solve": (_ip, [_vp, _ip, _vp, _lp, _vp, _lp, _vp, _ip, _dp, _dp, _ip, _dp, _PI, _PD, _PD]),
+        "hpccg_hip_srpoly_bound": (_ip, [_vp, _vp, _PD]),
+        "hpccg_hip_srpoly_last_spectrum": (_ip, [_vp, _PD, _PD]),
+        "hpccg_hip_srpoly_last_trace": (_ip, [_vp, _ip, _PD, _ip]),
+        "hpccg_hip_srpoly_release": (_ip, [_vp]),
+        "hpccg_hip_srpoly_workspace_bytes": (_ip, [_vp, _PL]),
+        "hpccg_hip_srpoly_live_workspaces": (_ip, [_PI]),
+    })
+
+
+SRPOLY_GROUP_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_srpoly_group.so")
+
+
+def srpoly_group_lib() -> C.CDLL:
+    """Load libhpccg_hip_srpoly_group.so (include/hpccg_hip_srpoly_group.h) on
+    first use. It is linked against libhpccg_hip.so beside it, so lib() is
+    loaded first and both share one copy of the main library."""
+    return _load_unit("srpoly_group", SRPOLY_GROUP_LIB_PATH, "the group srpoly library", "the group single-reduction polynomial solve has no fallback", {
+        "hpccg_hip_group_srpoly_abi_version": (_ip, []),
+        "hpccg_hip_group_srpoly_solve_device": (_ip, [_PV, _ip, _ip, _PV, _PL, _PV, _PL, _PV, _ip, _dp, _dp, _ip, _dp, _PI, _PD, _PD]),
+        "hpccg_hip_group_srpoly_bound": (_ip, [_PV, _ip, _PV, _PD]),
+        "hpccg_hip_group_srpoly_last_spectrum": (_ip, [_PV, _ip, _PD, _PD]),
+        "hpccg_hip_group_srpoly_last_trace": (_ip, [_PV, _ip, _ip, _PD, _ip]),
+        "hpccg_hip_group_srpoly_release": (_ip, [_vp]),
+        "hpccg_hip_group_srpoly_workspace_bytes": (_ip, [_vp, _PL]),
+        "hpccg_hip_group_srpoly_live_workspaces": (_ip, [_PI]),
+    })
+
+
 POLY_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_poly.so")
 
 
@@ -385,6 +424,16 @@ def group_poly32_exported_symbols() -> list[str]:
 def poly32_exported_symbols() -> list[str]:
     """Functions include/hpccg_hip_poly32.h declares (checked by the CPU suite)."""
     return _declared("hpccg_hip_poly32.h", r"\b(hpccg_hip_poly32_\w+)\s*\(")
+
+
+def group_srpoly_exported_symbols() -> list[str]:
+    """Functions include/hpccg_hip_srpoly_group.h declares (checked by the CPU suite)."""
+    return _declared("hpccg_hip_srpoly_group.h", r"\b(hpccg_hip_group_srpoly_\w+)\s*\(")
+
+
+def srpoly_exported_symbols() -> list[str]:
+    """Functions include/hpccg_hip_srpoly.h declares (checked by the CPU suite)."""
+    return _declared("hpccg_hip_srpoly.h", r"\b(hpccg_hip_srpoly_\w+)\s*\(")
 
 
 def group_poly_exported_symbols() -> list[str]:
@@ -812,6 +861,27 @@ class Matrix:
     def poly_workspace_bytes(self) -> int:
         return _workspace_bytes("poly", "poly_workspace_bytes", self.h)
 
+    def last_trace_srpoly(self, col: int, cap: int = 100000) -> np.ndarray:
+        """Residual trace (norm of r) of column col of the last HPCCG_srpoly on this matrix."""
+        out = np.zeros(cap, np.float64)
+        n = srpoly_lib().hpccg_hip_srpoly_last_trace(self.h, int(col), out.ctypes.data_as(C.POINTER(C.c_double)), cap)
+        if n < 0:
+            _check(n, "last_trace_srpoly")
+        return out[:n]
+
+    def last_spectrum_srpoly(self) -> tuple:
+        """(lmin, lmax) the last HPCCG_srpoly on this matrix used."""
+        lo, hi = C.c_double(0.0), C.c_double(0.0)
+        _check(srpoly_lib().hpccg_hip_srpoly_last_spectrum(self.h, C.byref(lo), C.byref(hi)), "last_spectrum_srpoly")
+        return lo.value, hi.value
+
+    def srpoly_release(self) -> None:
+        """Free this matrix's srpoly workspace (with its cached 1 / a_ii and bound) now (close() does it too)."""
+        _release("srpoly", "srpoly_release", self.h)
+
+    def srpoly_workspace_bytes(self) -> int:
+        return _workspace_bytes("srpoly", "srpoly_workspace_bytes", self.h)
+
     def last_trace_poly32(self, col: int, cap: int = 100000) -> np.ndarray:
         """Residual trace (norm of r) of column col of the last HPCCG_poly32 on this matrix."""
         out = np.zeros(cap, np.float64)
@@ -1114,6 +1184,39 @@ def poly_bound(M: Matrix, minv=None) -> float:
 def poly_live_workspaces() -> int:
     """Matrices that hold a poly workspace (0 when the library was never loaded)."""
     return _live("poly", "poly_live_workspaces")
+
+
+# ---------------------------------------------------------------------------
+# single-reduction solve with the polynomial preconditioner (include/hpccg_hip_srpoly.h)
+# ---------------------------------------------------------------------------
+def HPCCG_srpoly(M: Matrix, B, X, degree: int = 2, lmin=None, lmax=None, minv=None, device=False,
+                 max_iter: int = 500, tolerance: float = 0.0, nrhs=None, ldb=None, ldx=None):
+    """HPCCG_poly in the single-reduction (Chronopoulos-Gear) form
+    (hpccg_hip_srpoly_solve[_device]): the three dots of an iteration are
+    completed at one point, 3 + degree launches per iteration, for two more
+    vectors. Degree 0 is HPCCG_srcg bit for bit; the first iteration
+    (max_iter <= 2) is HPCCG_poly bit for bit with the same interval; later
+    ones agree to rounding. Arguments and return: HPCCG_poly's. X is updated in
+    place."""
+    L = srpoly_lib()
+    return _column_solve("HPCCG_srpoly", L.hpccg_hip_srpoly_solve_device if device else L.hpccg_hip_srpoly_solve, M, B, X, minv,
+                         device, nrhs, ldb, ldx, int(degree), 0.0 if lmin is None else float(lmin),
+                         0.0 if lmax is None else float(lmax), max_iter, tolerance)
+
+
+def srpoly_bound(M: Matrix, minv=None) -> float:
+    """The symmetric Gershgorin bound that HPCCG_srpoly takes for lmax
+    (poly_bound's value); minv: a device tensor / pointer of nrow entries, or
+    None for Jacobi."""
+    mp, keep = (None, None) if minv is None else _minv_ptr(M, minv, True)
+    v = C.c_double(0.0)
+    _check(srpoly_lib().hpccg_hip_srpoly_bound(M.h, mp, C.byref(v)), "srpoly_bound")
+    return v.value
+
+
+def srpoly_live_workspaces() -> int:
+    """Matrices that hold a srpoly workspace (0 when the library was never loaded)."""
+    return _live("srpoly", "srpoly_live_workspaces")
 
 
 # ---------------------------------------------------------------------------
@@ -1562,6 +1665,58 @@ def group_srcg_release(M: Matrix) -> None:
 def group_srcg_live_workspaces() -> int:
     """Matrices that hold a group srcg workspace (0 when the library was never loaded)."""
     return _live("srcg_group", "group_srcg_live_workspaces")
+
+
+# ---------------------------------------------------------------------------
+# ... with the polynomial preconditioner (include/hpccg_hip_srpoly_group.h)
+# ---------------------------------------------------------------------------
+def group_HPCCG_srpoly(Ms: list, Bs, Xs, degree: int = 2, lmin=None, lmax=None, minvs=None, max_iter: int = 500,
+                       tolerance: float = 0.0, nrhs=None, ldb=None, ldx=None, halo_copies: bool = False):
+    """group_HPCCG_poly in the single-reduction form
+    (hpccg_hip_group_srpoly_solve_device): degree + 1 halos per iteration, as
+    there, and one sum over the members instead of two. Degree 0 is
+    group_HPCCG_srcg bit for bit; the first iteration (max_iter <= 2) is
+    group_HPCCG_poly bit for bit; a group of one is HPCCG_srpoly bit for bit.
+    The arguments and the result are group_HPCCG_poly's. halo_copies
+    (diagnostic): move every ghost plane of z and u by one copy per column and
+    side instead of one kernel launch per member; the bits are the same."""
+    return _group_solve("group_HPCCG_srpoly", srpoly_group_lib().hpccg_hip_group_srpoly_solve_device,
+                        "HPCCG_GROUP_SRPOLY_HALO_COPIES", Ms, Bs, Xs, minvs, nrhs, ldb, ldx, halo_copies,
+                        *_interval(degree, lmin, lmax), max_iter, tolerance)
+
+
+def group_srpoly_bound(Ms: list, minvs=None) -> float:
+    """The symmetric Gershgorin bound of the group's global matrix that
+    group_HPCCG_srpoly takes for lmax (group_poly_bound's value); minvs: per
+    member a device tensor / pointer of its nrow entries, or None for Jacobi."""
+    return _group_bound("group_srpoly_bound", srpoly_group_lib().hpccg_hip_group_srpoly_bound, Ms, minvs)
+
+
+def group_last_trace_srpoly(Ms: list, col: int, cap: int = 100000) -> np.ndarray:
+    """Residual trace (norm of r) of column col of the last group_HPCCG_srpoly on Ms."""
+    return _group_last_trace("group_last_trace_srpoly", srpoly_group_lib().hpccg_hip_group_srpoly_last_trace, Ms, col,
+                             cap)
+
+
+def group_last_spectrum_srpoly(Ms: list) -> tuple:
+    """(lmin, lmax) the last group_HPCCG_srpoly on Ms used."""
+    return _group_last_spectrum("group_last_spectrum_srpoly", srpoly_group_lib().hpccg_hip_group_srpoly_last_spectrum,
+                                Ms)
+
+
+def group_srpoly_workspace_bytes(M: Matrix) -> int:
+    """Device bytes member M's group srpoly workspace holds (0: none)."""
+    return _workspace_bytes("srpoly_group", "group_srpoly_workspace_bytes", M.h)
+
+
+def group_srpoly_release(M: Matrix) -> None:
+    """Free member M's group srpoly workspace (with its caches) now (close() does it too)."""
+    _release("srpoly_group", "group_srpoly_release", M.h)
+
+
+def group_srpoly_live_workspaces() -> int:
+    """Matrices that hold a group srpoly workspace (0 when the library was never loaded)."""
+    return _live("srpoly_group", "group_srpoly_live_workspaces")
 
 
 def HPC_sparsemv(M: Matrix, x, y) -> int:

@@ -10,6 +10,10 @@
 // columns and fp64 SpMM form, the init, SpMM and finalize launchers, the matrix
 // check, the preconditioner, the solve, the bookkeeping exports -- is
 // hpccg_onerank_host.h.
+// The single-reduction units (hpccg_srpoly.hip, hpccg_srpoly_group.hip) take the
+// workspace, the arguments, the step launchers, the bound and the interval from
+// here and run a launch loop and a solve of their own; their workspaces add
+// vectors through ensure_vectors' last argument.
 // A unit hands over one traits struct U: what hpccg_onerank_host.h asks for
 // (Args a PolyArgs, Workspace a PolyWorkspace) and
 //   row0(w)               local row 0 inside a guarded column: the guard rows
@@ -244,8 +248,11 @@ int jacobi_bound(typename U::Workspace* w, double* lmax)
 }
 
 // Room for ncols columns of the guarded width pcs and a history of max_iter + 1
-// entries per column; ntot: totals per column (a group member's).
-int ensure_vectors(PolyWorkspace* w, int ncols, int max_iter, long long pcs, int ntot)
+// entries per column; ntot: totals per column (a group member's). more(cap):
+// allocates what a unit's workspace W adds to the polynomial's vectors (the
+// single-reduction units: p and s), last.
+template <class W, class More>
+int ensure_vectors(W* w, int ncols, int max_iter, long long pcs, int ntot, More more)
 {
     const size_t npad = (size_t)w->v.npad;
     return ensure_columns(w, ncols, max_iter, true, pcs, ntot, [&](int cap) {
@@ -256,8 +263,13 @@ int ensure_vectors(PolyWorkspace* w, int ncols, int max_iter, long long pcs, int
         // zeroed: z's guard zones and the rows past n are read and never stored
         // (a member's ghost planes by the halo only)
         TRY(alloc_zero(w, &w->zbuf, 2 * (size_t)pcs * cap));
-        return 0;
+        return more(cap);
     });
+}
+
+inline int ensure_vectors(PolyWorkspace* w, int ncols, int max_iter, long long pcs, int ntot)
+{
+    return ensure_vectors(w, ncols, max_iter, pcs, ntot, [](int) { return 0; });
 }
 
 // The update with step 0, then steps 1 .. d: z_d ends in buffer d & 1.

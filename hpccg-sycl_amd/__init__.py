@@ -1156,6 +1156,26 @@ def srcg_live_workspaces() -> int:
 # ---------------------------------------------------------------------------
 # Chebyshev polynomial preconditioned solve (include/hpccg_hip_poly.h)
 # ---------------------------------------------------------------------------
+def _interval(degree, lmin, lmax):
+    """degree, lmin, lmax as the polynomial libraries take them (0.0: the default)."""
+    return int(degree), 0.0 if lmin is None else float(lmin), 0.0 if lmax is None else float(lmax)
+
+
+def _poly_solve(what, L, unit, M, B, X, degree, lmin, lmax, minv, device, max_iter, tolerance, nrhs, ldb, ldx):
+    """What the one-rank polynomial solves share: library L's
+    hpccg_hip_<unit>_solve[_device] through _column_solve."""
+    solve = getattr(L, f"hpccg_hip_{unit}_solve_device" if device else f"hpccg_hip_{unit}_solve")
+    return _column_solve(what, solve, M, B, X, minv, device, nrhs, ldb, ldx, *_interval(degree, lmin, lmax), max_iter,
+                         tolerance)
+
+
+def _poly_bound(what, bound, M, minv):
+    mp, keep = (None, None) if minv is None else _minv_ptr(M, minv, True)
+    v = C.c_double(0.0)
+    _check(bound(M.h, mp, C.byref(v)), what)
+    return v.value
+
+
 def HPCCG_poly(M: Matrix, B, X, degree: int = 2, lmin=None, lmax=None, minv=None, device=False, max_iter: int = 500,
                tolerance: float = 0.0, nrhs=None, ldb=None, ldx=None):
     """nrhs CG solves against M preconditioned by the Chebyshev polynomial of
@@ -1165,20 +1185,15 @@ def HPCCG_poly(M: Matrix, B, X, degree: int = 2, lmin=None, lmax=None, minv=None
     verified. The loop test, niters and normr are on the 2-norm of r, as in
     HPCCG. B, X, minv: as HPCCG_pcg. X is updated in place. Returns
     (ierr, niters[nrhs], normr[nrhs], times)."""
-    L = poly_lib()
-    return _column_solve("HPCCG_poly", L.hpccg_hip_poly_solve_device if device else L.hpccg_hip_poly_solve, M, B, X, minv,
-                         device, nrhs, ldb, ldx, int(degree), 0.0 if lmin is None else float(lmin),
-                         0.0 if lmax is None else float(lmax), max_iter, tolerance)
+    return _poly_solve("HPCCG_poly", poly_lib(), "poly", M, B, X, degree, lmin, lmax, minv, device, max_iter, tolerance,
+                       nrhs, ldb, ldx)
 
 
 def poly_bound(M: Matrix, minv=None) -> float:
     """The symmetric Gershgorin bound on the spectrum of diag(minv) A that
     HPCCG_poly takes for lmax; minv: a device tensor / pointer of nrow entries,
     or None for Jacobi."""
-    mp, keep = (None, None) if minv is None else _minv_ptr(M, minv, True)
-    v = C.c_double(0.0)
-    _check(poly_lib().hpccg_hip_poly_bound(M.h, mp, C.byref(v)), "poly_bound")
-    return v.value
+    return _poly_bound("poly_bound", poly_lib().hpccg_hip_poly_bound, M, minv)
 
 
 def poly_live_workspaces() -> int:
@@ -1198,20 +1213,15 @@ def HPCCG_srpoly(M: Matrix, B, X, degree: int = 2, lmin=None, lmax=None, minv=No
     (max_iter <= 2) is HPCCG_poly bit for bit with the same interval; later
     ones agree to rounding. Arguments and return: HPCCG_poly's. X is updated in
     place."""
-    L = srpoly_lib()
-    return _column_solve("HPCCG_srpoly", L.hpccg_hip_srpoly_solve_device if device else L.hpccg_hip_srpoly_solve, M, B, X, minv,
-                         device, nrhs, ldb, ldx, int(degree), 0.0 if lmin is None else float(lmin),
-                         0.0 if lmax is None else float(lmax), max_iter, tolerance)
+    return _poly_solve("HPCCG_srpoly", srpoly_lib(), "srpoly", M, B, X, degree, lmin, lmax, minv, device, max_iter, tolerance,
+                       nrhs, ldb, ldx)
 
 
 def srpoly_bound(M: Matrix, minv=None) -> float:
     """The symmetric Gershgorin bound that HPCCG_srpoly takes for lmax
     (poly_bound's value); minv: a device tensor / pointer of nrow entries, or
     None for Jacobi."""
-    mp, keep = (None, None) if minv is None else _minv_ptr(M, minv, True)
-    v = C.c_double(0.0)
-    _check(srpoly_lib().hpccg_hip_srpoly_bound(M.h, mp, C.byref(v)), "srpoly_bound")
-    return v.value
+    return _poly_bound("srpoly_bound", srpoly_lib().hpccg_hip_srpoly_bound, M, minv)
 
 
 def srpoly_live_workspaces() -> int:
@@ -1230,20 +1240,15 @@ def HPCCG_poly32(M: Matrix, B, X, degree: int = 2, lmin=None, lmax=None, minv=No
     fp64 one. Where the image is exact (poly32_info) every column is HPCCG_poly
     bit for bit; degree 0 is HPCCG_pcg bit for bit on any matrix. A matrix
     outside fp32 range is refused. Arguments and return: HPCCG_poly's."""
-    L = poly32_lib()
-    return _column_solve("HPCCG_poly32", L.hpccg_hip_poly32_solve_device if device else L.hpccg_hip_poly32_solve, M, B, X, minv,
-                         device, nrhs, ldb, ldx, int(degree), 0.0 if lmin is None else float(lmin),
-                         0.0 if lmax is None else float(lmax), max_iter, tolerance)
+    return _poly_solve("HPCCG_poly32", poly32_lib(), "poly32", M, B, X, degree, lmin, lmax, minv, device, max_iter, tolerance,
+                       nrhs, ldb, ldx)
 
 
 def poly32_bound(M: Matrix, minv=None) -> float:
     """The symmetric Gershgorin bound of the fp64 image that HPCCG_poly32 takes
     for lmax (poly_bound's value); minv: a device tensor / pointer of nrow
     entries, or None for Jacobi."""
-    mp, keep = (None, None) if minv is None else _minv_ptr(M, minv, True)
-    v = C.c_double(0.0)
-    _check(poly32_lib().hpccg_hip_poly32_bound(M.h, mp, C.byref(v)), "poly32_bound")
-    return v.value
+    return _poly_bound("poly32_bound", poly32_lib().hpccg_hip_poly32_bound, M, minv)
 
 
 def poly32_info(M: Matrix) -> dict:
@@ -1514,11 +1519,6 @@ def group_pcg_live_workspaces() -> int:
 # ---------------------------------------------------------------------------
 # polynomial preconditioned solve over an in-process group (include/hpccg_hip_poly_group.h)
 # ---------------------------------------------------------------------------
-def _interval(degree, lmin, lmax):
-    """degree, lmin, lmax as the polynomial libraries take them (0.0: the default)."""
-    return int(degree), 0.0 if lmin is None else float(lmin), 0.0 if lmax is None else float(lmax)
-
-
 def group_HPCCG_poly(Ms: list, Bs, Xs, degree: int = 2, lmin=None, lmax=None, minvs=None, max_iter: int = 500,
                      tolerance: float = 0.0, nrhs=None, ldb=None, ldx=None, halo_copies: bool = False):
     """nrhs CG solves over an in-process group preconditioned by the Chebyshev

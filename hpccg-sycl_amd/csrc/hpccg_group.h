@@ -382,7 +382,7 @@ int group_sum(const Group<W, A>& G, const GroupTotals& gt, int which, const Grou
 }
 
 // The frame of a unit's launch loop over the group (group_run_cg below,
-// group_run_srcg in hpccg_srcg_group.hip).
+// group_run_srcg in hpccg_srcg_group_host.h).
 // What the sum kernel reads and stores on the members.
 template <class W, class A>
 GroupTotals group_totals(const Group<W, A>& G)

@@ -5,7 +5,8 @@
 // preconditioner with its refusals, the argument checks of solve_device, the
 // staging around a unit's launch loop and the body of last_trace; for the two
 // units without a polynomial (pcg, srcg) also the member's workspace, its
-// vectors, the shared kernel arguments and the whole solve. It stands on
+// vectors, the shared kernel arguments and the whole solve. The launch loop
+// of the single-reduction group units is hpccg_srcg_group_host.h. It stands on
 // hpccg_group.h (the group engine) and hpccg_onerank_host.h (the launch
 // dispatch, the bookkeeping bodies).
 // A unit hands over one traits struct U: Args, Workspace (a TraceWorkspace, a

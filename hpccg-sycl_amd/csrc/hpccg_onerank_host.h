@@ -1,6 +1,7 @@
 // hpccg_onerank_host.h -- the host code that the units solving on one rank
 // share (hpccg_pcg.hip, hpccg_srcg.hip and, through hpccg_poly_host.h,
-// hpccg_poly.hip and hpccg_poly32.hip): the dispatch of a launch on a chunk's
+// hpccg_poly.hip, hpccg_poly32.hip and hpccg_srpoly.hip; the single-reduction
+// launch loop over it is hpccg_srcg_host.h): the dispatch of a launch on a chunk's
 // columns and fp64 SpMM form, the matrix check, the diagonal preconditioner
 // with its refusals, the solve (argument checks, the empty matrix, staging B
 // and X, the two `times` slots) and the bodies of the bookkeeping exports.

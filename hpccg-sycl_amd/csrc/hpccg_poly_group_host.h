@@ -1,6 +1,7 @@
 // hpccg_poly_group_host.h -- the host code of the Chebyshev polynomial
 // preconditioned CG over an in-process rank group, shared by the polynomial
-// group units (hpccg_poly_group.hip, hpccg_poly32_group.hip): what is
+// group units (hpccg_poly_group.hip, hpccg_poly32_group.hip and, with its own
+// recurrence in solve_device's slots, hpccg_srpoly_group.hip): what is
 // polynomial in them -- the members' bound, the group's update phase with the
 // halos of z (group_poly_update: the ordering argument is written there), the
 // interval of a solve and the bodies of solve_device, bound and last_spectrum.
@@ -170,23 +171,39 @@ int group_poly_update(const GroupOf<U>& G, int nrhs, bool prologue, HaloLaunch h
 // ---------------------------------------------------------------------------
 // The bodies of a unit's extern "C" functions
 // ---------------------------------------------------------------------------
+// The polynomial CG's launch loop: hpccg_group.h's, with the update phase above.
+template <class U>
+int group_poly_run(const GroupOf<U>& G, int nrhs, int max_iter, double tol, HaloLaunch halo, int* niters,
+                   double* normr, double* wall)
+{
+    const GroupLaunch<typename U::Workspace, typename U::Args> launch = {
+        launch_init<U>,     launch_p<U>,         U::launch_spmm, launch_update0<U>,
+        launch_finalize<U>, launch_group_sum<U>, halo,           group_poly_update<U>};
+    return group_run_cg(G, nrhs, max_iter, tol, launch, niters, normr, wall);
+}
+
 // hpccg_group_host.h's solve_device with the degree and the bounds checked
 // after the arrays, and the interval resolved once every member's m is in hand.
+// Where a unit differs (the single-reduction unit, hpccg_srcg_group_host.h):
+// more(w, cap) (may be null) allocates what its workspace adds to the
+// polynomial's vectors, member_args are a member's kernel arguments, run is its
+// launch loop.
 template <class U>
 int group_poly_solve_device(hpccg_hip_matrix* const* Ms, int nranks, int nrhs, const double* const* B_dev,
                             const long long* ldb, double* const* X_dev, const long long* ldx,
                             const double* const* minv_dev, int degree, double lmin, double lmax, int max_iter,
-                            double tolerance, int* niters, double* normr, double* times)
+                            double tolerance, int* niters, double* normr, double* times,
+                            int (*more)(typename U::Workspace*, int cap) = nullptr,
+                            typename U::Args (*member_args)(const typename U::Workspace*, int, const double*) =
+                                make_args<U>,
+                            int (*run)(const GroupOf<U>&, int nrhs, int max_iter, double tol, HaloLaunch halo,
+                                       int* niters, double* normr, double* wall) = group_poly_run<U>)
 {
     using W = typename U::Workspace;
     const char* who = U::who;
     return group_solve_device<U>(
         Ms, nranks, nrhs, B_dev, ldb, X_dev, ldx, minv_dev, max_iter, niters, normr, times, true,
-        [&]() -> int {
-            if (degree < 0 || degree > kPolyMaxDegree)
-                return fail(HPCCG_HIP_EINVAL, "%s: degree %d (0 to %d)", who, degree, kPolyMaxDegree);
-            return check_bounds(who, lmin, lmax);
-        },
+        [&] { return check_polynomial(who, degree, lmin, lmax); },
         [&](GroupOf<U>& G, int kmax) -> int {
             const HaloLaunch halo = halo_launcher<U>();
             // the preconditioner and the interval first, on every member: a
@@ -200,22 +217,19 @@ int group_poly_solve_device(hpccg_hip_matrix* const* Ms, int nranks, int nrhs, c
             }));
             for (int r = 0; r < G.P; r++) {
                 W* w = G.w[r];
-                TRY(ensure_vectors(w, nrhs, kmax, guarded_p_column(w->v).pcs, 3));
+                TRY(ensure_vectors(w, nrhs, kmax, guarded_p_column(w->v).pcs, 3,
+                                   [&](int cap) { return more ? more(w, cap) : 0; }));
                 w->degree = degree;
                 w->cheb0 = cheb0;
                 std::copy(aj, aj + kPolyMaxDegree + 1, w->aj);
                 std::copy(bj, bj + kPolyMaxDegree + 1, w->bj);
-                G.a[r] = make_args<U>(w, nrhs, m[r]);
+                G.a[r] = member_args(w, nrhs, m[r]);
             }
             G.w[0]->last_lmin = lmin;
             G.w[0]->last_lmax = lmax;
             G.w[0]->solved = true;
-            const GroupLaunch<W, typename U::Args> launch = {launch_init<U>,      launch_p<U>,
-                                                             U::launch_spmm,      launch_update0<U>,
-                                                             launch_finalize<U>,  launch_group_sum<U>,
-                                                             halo,                group_poly_update<U>};
             return group_run_staged(G, nrhs, B_dev, ldb, X_dev, ldx, times, [&](double* wall) {
-                return group_run_cg(G, nrhs, kmax, tolerance, launch, niters, normr, wall);
+                return run(G, nrhs, kmax, tolerance, halo, niters, normr, wall);
             });
         });
 }

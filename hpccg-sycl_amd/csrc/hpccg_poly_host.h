@@ -10,10 +10,10 @@
 // columns and fp64 SpMM form, the init, SpMM and finalize launchers, the matrix
 // check, the preconditioner, the solve, the bookkeeping exports -- is
 // hpccg_onerank_host.h.
-// The single-reduction units (hpccg_srpoly.hip, hpccg_srpoly_group.hip) take the
-// workspace, the arguments, the step launchers, the bound and the interval from
-// here and run a launch loop and a solve of their own; their workspaces add
-// vectors through ensure_vectors' last argument.
+// The single-reduction units (hpccg_srpoly.hip, hpccg_srpoly_group.hip) run the
+// solve bodies here and in hpccg_poly_group_host.h with vectors of their own
+// (p and s) and their own recurrence (hpccg_srcg_host.h,
+// hpccg_srcg_group_host.h) in the bodies' slots.
 // A unit hands over one traits struct U: what hpccg_onerank_host.h asks for
 // (Args a PolyArgs, Workspace a PolyWorkspace) and
 //   row0(w)               local row 0 inside a guarded column: the guard rows
@@ -172,6 +172,14 @@ int check_bounds(const char* who, double lmin, double lmax)
     return 0;
 }
 
+// A caller's degree and bounds: what a solve checks before it looks at a matrix.
+int check_polynomial(const char* who, int degree, double lmin, double lmax)
+{
+    if (degree < 0 || degree > kPolyMaxDegree)
+        return fail(HPCCG_HIP_EINVAL, "%s: degree %d (0 to %d)", who, degree, kPolyMaxDegree);
+    return check_bounds(who, lmin, lmax);
+}
+
 // The interval of a call and the polynomial's coefficients on it. *lmax == 0.0:
 // bound(lmax), the unit's Gershgorin bound; *lmin == 0.0: lmax / kPolyEigRatio.
 // Degree 0 applies no polynomial and needs no interval (what the caller gave is
@@ -250,7 +258,7 @@ int jacobi_bound(typename U::Workspace* w, double* lmax)
 // Room for ncols columns of the guarded width pcs and a history of max_iter + 1
 // entries per column; ntot: totals per column (a group member's). more(cap):
 // allocates what a unit's workspace W adds to the polynomial's vectors (the
-// single-reduction units: p and s), last.
+// single-reduction units: p and s, hpccg_srcg_host.h), last.
 template <class W, class More>
 int ensure_vectors(W* w, int ncols, int max_iter, long long pcs, int ntot, More more)
 {
@@ -265,11 +273,6 @@ int ensure_vectors(W* w, int ncols, int max_iter, long long pcs, int ntot, More 
         TRY(alloc_zero(w, &w->zbuf, 2 * (size_t)pcs * cap));
         return more(cap);
     });
-}
-
-inline int ensure_vectors(PolyWorkspace* w, int ncols, int max_iter, long long pcs, int ntot)
-{
-    return ensure_vectors(w, ncols, max_iter, pcs, ntot, [](int) { return 0; });
 }
 
 // The update with step 0, then steps 1 .. d: z_d ends in buffer d & 1.
@@ -294,34 +297,33 @@ int run_cg(typename U::Workspace* w, int nrhs, const double* m, int max_iter, do
 
 // The solve: hpccg_onerank_host.h's, with the degree and the bounds checked
 // before the matrix and the interval resolved once m is in hand. prepare (may
-// be null): poly32's image.
+// be null): poly32's image. more(w, cap) (may be null): allocates what the
+// unit's workspace adds to the polynomial's vectors; run: its recurrence.
 template <class U>
 int solve_common(hpccg_hip_matrix* M, int nrhs, const double* B, long long ldb, double* X, long long ldx,
                  const double* minv, int degree, double lmin, double lmax, int max_iter, double tol, int* niters,
-                 double* normr, double* times, bool host, int (*prepare)(typename U::Workspace*) = nullptr)
+                 double* normr, double* times, bool host, int (*prepare)(typename U::Workspace*) = nullptr,
+                 int (*more)(typename U::Workspace*, int cap) = nullptr,
+                 int (*run)(typename U::Workspace*, int, const double*, int, double, int*, double*, double*) = run_cg<U>)
 {
     using W = typename U::Workspace;
     const char* who = U::who;
     return solve_onerank<U>(
         M, nrhs, B, ldb, X, ldx, minv, max_iter, tol, niters, normr, times, host,
-        [&]() -> int {
-            if (degree < 0 || degree > kPolyMaxDegree)
-                return fail(HPCCG_HIP_EINVAL, "%s: degree %d (0 to %d)", who, degree, kPolyMaxDegree);
-            return check_bounds(who, lmin, lmax);
-        },
+        [&] { return check_polynomial(who, degree, lmin, lmax); },
         prepare,
         [&](W* w, const double* m, int kmax) -> int {
             TRY(resolve_interval(who, degree, &lmin, &lmax, &w->cheb0, w->aj, w->bj, [&](double* top) {
                 return minv ? compute_bound<U>(w, m, top) : jacobi_bound<U>(w, top);
             }));
-            TRY(ensure_vectors(w, nrhs, kmax, p_column(w->v), 0));
+            TRY(ensure_vectors(w, nrhs, kmax, p_column(w->v), 0, [&](int cap) { return more ? more(w, cap) : 0; }));
             w->degree = degree;
             w->last_lmin = lmin;
             w->last_lmax = lmax;
             w->solved = true;
             return 0;
         },
-        run_cg<U>);
+        run);
 }
 
 // The bodies of a one-rank unit's bound and last_spectrum exports.

@@ -18,15 +18,16 @@
 //   diagonal  k_srcg_diag | k_srcg_check: hpccg_jacobi.h's bodies and cache
 // The step and the finalize are hpccg_srcg_bodies.h; the column's state, the
 // dot shapes, the workspace registry and the end of a recurrence are
-// hpccg_columns.h. The launch loop is this unit's; the host code around it --
+// hpccg_columns.h. The launch loop, its frame, the launchers and p and s are
+// hpccg_srcg_host.h, shared with hpccg_srpoly.hip; the host code around them --
 // the launch dispatch, the checks, the preconditioner, the solve, the
 // bookkeeping exports -- is hpccg_onerank_host.h, shared with hpccg_pcg.hip and
-// the polynomial units. No kernel here waits on another block.
+// the polynomial units. This unit keeps its kernel arguments. No kernel here
+// waits on another block.
 #include <hip/hip_runtime.h>
 
 #include "../../include/hpccg_hip_srcg.h"
-#include "hpccg_onerank_host.h"
-#include "hpccg_srcg_bodies.h"
+#include "hpccg_srcg_host.h"
 
 #pragma clang fp contract(off)
 
@@ -85,19 +86,19 @@ __global__ void k_srcg_check(const double* __restrict__ m, int n, int* bad)
 }
 
 // ---------------------------------------------------------------------------
-// host: hpccg_onerank_host.h over this unit's kernels, with its own launch loop
+// host: hpccg_srcg_host.h and hpccg_onerank_host.h over this unit's kernels
 // ---------------------------------------------------------------------------
-struct Workspace : TraceWorkspace, JacobiCache {
+struct Workspace : TraceWorkspace, JacobiCache, SrcgColumns {
     double *r = nullptr, *x = nullptr, *b = nullptr;
-    double *pd = nullptr, *sd = nullptr;  // p and s = A p (never zeroed again: k == 1 reads u and w)
 
     Workspace() { ndots = 3; }
 
     void free_own_vectors()
     {
-        for (double* q : {r, x, b, pd, sd})
+        for (double* q : {r, x, b})
             if (q) (void)hipFree(q);
-        r = x = b = pd = sd = nullptr;
+        r = x = b = nullptr;
+        free_ps();
     }
     void free_own_rest() { free_cache(); }
     long long total_bytes() const { return bytes + rest_bytes; }
@@ -112,9 +113,7 @@ int ensure_vectors(Workspace* w, int ncols, int max_iter)
         TRY(alloc_zero(w, &w->r, npad * cap));
         TRY(alloc_zero(w, &w->x, npad * cap));
         TRY(alloc_zero(w, &w->b, npad * cap));
-        TRY(alloc_zero(w, &w->pd, npad * cap));
-        TRY(alloc_zero(w, &w->sd, npad * cap));
-        return 0;
+        return alloc_ps(w, npad * cap);
     });
 }
 
@@ -144,68 +143,28 @@ struct Srcg {
     static constexpr const char* solve_name = "single-reduction";
 
     static constexpr auto init = k_srcg_init;
+    template <int kR>
+    static constexpr auto t = k_srcg_t<kR>;
+    template <int kR>
+    static auto fused_step(const Workspace*)
+    {
+        return k_srcg_step<kR>;
+    }
     // (prologue: no u.w partial, the SpMM of t)
     template <int kW, int kR, int kWaves>
     static constexpr auto spmm_a = k_srcg_spmm_a<kW, kR, kWaves>;
     template <int kR>
     static constexpr auto spmm_sell = k_srcg_spmm_sell<kR>;
+    static constexpr auto finalize = k_srcg_finalize;
     static constexpr auto diag = k_srcg_diag;
     static constexpr auto check = k_srcg_check;
 };
 
-void launch_t(const Workspace* w, const SrcgArgs& a)
-{
-    // (prologue: col_p's form)
-    launch_chunks(w, a, true, [](auto r) { return k_srcg_t<decltype(r)::value>; });
-}
-
-void launch_step(const Workspace* w, const SrcgArgs& a, bool prologue)
-{
-    launch_chunks(w, a, prologue, [](auto r) { return k_srcg_step<decltype(r)::value>; });
-}
-
-void launch_finalize(const Workspace* w, const SrcgArgs& a)
-{
-    hipLaunchKernelGGL(k_srcg_finalize, dim3(a.nrhs), dim3(kFinThreads), 0, w->v.stream, a, 0);
-}
-
-// One recurrence per column of the states on the device, on (b, x) of a: the
-// prologue (t, A t, r and u, A u, the three totals), then iterations
-// 1 .. kmax - 1 of step, SpMM, finalize, launched eagerly on the matrix's
-// stream. Every kCheckEvery iterations the host reads the "columns ended" word
-// and stops launching once every column has ended.
-int run_iterations(Workspace* w, const SrcgArgs& a, int nrhs, int kmax)
-{
-    hipStream_t s = w->v.stream;
-    launch_t(w, a);
-    launch_spmm64<Srcg>(w, a, true);
-    launch_step(w, a, true);
-    launch_spmm64<Srcg>(w, a, false);
-    launch_finalize(w, a);
-    HIP_TRY(hipGetLastError());
-    for (int k = 1; k < kmax; k++) {
-        launch_step(w, a, false);
-        launch_spmm64<Srcg>(w, a, false);
-        launch_finalize(w, a);
-        if (k % kCheckEvery == 0 && k + 1 < kmax) {
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(w->h_ended, w->ended, sizeof(int), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            if (*w->h_ended >= nrhs) break;  // later launches would be no-ops for every column
-        }
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
 // The single-reduction CG on the columns staged in the workspace's b and x.
 int run_cg(Workspace* w, int nrhs, const double* m, int max_iter, double tol, int* niters, double* normr, double* wall)
 {
-    const SrcgArgs a = make_args(w, nrhs, m);
-    HIP_TRY(hipEventRecord(w->ev0, w->v.stream));
-    launch_init<Srcg>(w, a, max_iter, tol);
-    TRY(run_iterations(w, a, nrhs, max_iter));
-    return finish_recurrence(w, nrhs, niters, normr, wall);
+    return run_srcg<Srcg>(w, make_args(w, nrhs, m), nrhs, max_iter, tol, niters, normr, wall, launch_srcg_step<Srcg>,
+                          launch_spmm64<Srcg>);
 }
 
 int solve_common(hpccg_hip_matrix* M, int nrhs, const double* B, long long ldb, double* X, long long ldx,

@@ -29,14 +29,15 @@
 // hpccg_group.h; the dispatch of a launch on a chunk's columns and SpMM form
 // and the bookkeeping exports are hpccg_onerank_host.h; the member's workspace
 // and preconditioner, the argument checks and the solve are hpccg_group_host.h,
-// shared with hpccg_pcg_group.hip; this unit adds p and s, the sum kernel and
-// the launch loop. Ordering between the members is by stream events. No kernel
-// here waits on another block.
+// shared with hpccg_pcg_group.hip; p and s, the launchers, the sum kernel's
+// body, the fence between neighbours and the launch loop are
+// hpccg_srcg_group_host.h (over hpccg_srcg_host.h), shared with
+// hpccg_srpoly_group.hip. Ordering between the members is by stream events. No
+// kernel here waits on another block.
 #include <hip/hip_runtime.h>
 
 #include "../../include/hpccg_hip_srcg_group.h"
-#include "hpccg_group_host.h"
-#include "hpccg_srcg_bodies.h"
+#include "hpccg_srcg_group_host.h"
 
 #pragma clang fp contract(off)
 
@@ -89,24 +90,10 @@ __global__ __launch_bounds__(kFinThreads) void k_srcg_group_finalize(SrcgArgs a,
     srcg_finalize(a, store_total);
 }
 
-// The group's three dots and the column's state on every member: one thread
-// per column on member 0's stream, after every member's local finalize. Each
-// dot is the members' local totals added in rank order from 0.0 (col_group_sum's
-// sum); the column advances once, as in the one-rank finalize, and its state is
-// stored into every member's state array, so all members freeze a column
-// together. hist and the "columns ended" word are member 0's (a: its args).
+// The group's three dots and the column's state on every member (hpccg_srcg_group_host.h).
 __global__ void k_srcg_group_sum(SrcgArgs a, GroupTotals g)
 {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= a.nrhs) return;
-    ColState s = a.st[c];
-    if (!s.run) return;  // frozen on every member
-    double rr = 0.0, gamma = 0.0, delta = 0.0;
-    for (int r = 0; r < g.nranks; r++) rr += g.tot[r][(size_t)kDotRR * g.cap[r] + c];
-    for (int r = 0; r < g.nranks; r++) gamma += g.tot[r][(size_t)kDotRZ * g.cap[r] + c];
-    for (int r = 0; r < g.nranks; r++) delta += g.tot[r][(size_t)kDotPAP * g.cap[r] + c];
-    srcg_advance(a, &s, c, rr, gamma, delta);
-    for (int r = 0; r < g.nranks; r++) g.st[r][c] = s;
+    srcg_group_sum(a, g);
 }
 
 // The halo of every column's u (in the prologue: t) in one launch per member (hpccg_group.h).
@@ -133,30 +120,22 @@ __global__ void k_srcg_group_check(const double* __restrict__ m, int n, int* bad
 // One member's workspace: the columns (u's guarded, with the member's ghost
 // planes), p and s, the cached 1 / a_ii with its verdict and a slot for a
 // caller's m. The member's other workspaces are other records.
-struct Workspace : GroupWorkspace {
-    double *pd = nullptr, *sd = nullptr;  // p and s = A p (never zeroed again: k == 1 reads u and w)
-
+struct Workspace : GroupWorkspace, SrcgColumns {
     void free_own_vectors()
     {
         GroupWorkspace::free_own_vectors();
-        for (double* q : {pd, sd})
-            if (q) (void)hipFree(q);
-        pd = sd = nullptr;
+        free_ps();
     }
 };
 
-// hpccg_group_host.h's and hpccg_onerank_host.h's host code over this unit's kernels
+// hpccg_srcg_group_host.h's, hpccg_group_host.h's and hpccg_onerank_host.h's host code over this unit's kernels
 struct SrcgGroupUnit {
     using Args = SrcgArgs;
     using Workspace = hpccg::Workspace;
     static constexpr const char* who = "group srcg";
     // diagnostics: the halo by copies, the A/B of k_srcg_group_halo (tools/group_srcg_bench.py)
     static constexpr const char* halo_env = "HPCCG_GROUP_SRCG_HALO_COPIES";
-    static int own_vectors(Workspace* w, size_t count)
-    {
-        TRY(alloc_zero(w, &w->pd, count));
-        return alloc_zero(w, &w->sd, count);
-    }
+    static int own_vectors(Workspace* w, size_t count) { return alloc_ps(w, count); }
     static SrcgArgs make_args(const Workspace* w, int nrhs, const double* m)
     {
         SrcgArgs a{};
@@ -167,110 +146,31 @@ struct SrcgGroupUnit {
     }
 
     static constexpr auto init = k_srcg_group_init;
+    template <int kR>
+    static constexpr auto t = k_srcg_group_t<kR>;
+    template <int kR>
+    static auto fused_step(const Workspace*)
+    {
+        return k_srcg_group_step<kR>;
+    }
     template <int kW, int kR, int kWaves>
     static constexpr auto spmm_a = k_srcg_group_spmm_a<kW, kR, kWaves>;
     template <int kR>
     static constexpr auto spmm_sell = k_srcg_group_spmm_sell<kR>;
+    static constexpr auto finalize = k_srcg_group_finalize;
+    static constexpr auto sum = k_srcg_group_sum;
     static constexpr auto halo = k_srcg_group_halo;
     static constexpr auto diag = k_srcg_group_diag;
     static constexpr auto check = k_srcg_group_check;
 };
 using SrcgGroup = GroupOf<SrcgGroupUnit>;
 
-void launch_t(const Workspace* w, const SrcgArgs& a)
+// The launch loop with u in p's buffer: the prologue fences, and nothing runs between the step and the halo of u.
+int group_run(const SrcgGroup& G, int nrhs, int max_iter, double tol, HaloLaunch halo, int* niters, double* normr,
+              double* wall)
 {
-    // (prologue: col_p's form)
-    launch_chunks(w, a, true, [](auto r) { return k_srcg_group_t<decltype(r)::value>; });
-}
-
-void launch_step(const Workspace* w, const SrcgArgs& a, bool prologue)
-{
-    launch_chunks(w, a, prologue, [](auto r) { return k_srcg_group_step<decltype(r)::value>; });
-}
-
-// (store_total: always 1 here, a member's part; the state is the group sum's)
-void launch_finalize(const Workspace* w, const SrcgArgs& a)
-{
-    hipLaunchKernelGGL(k_srcg_group_finalize, dim3(a.nrhs), dim3(kFinThreads), 0, w->v.stream, a, 1);
-}
-
-// (which: group_sum's; the one launch sums all three dots)
-void launch_group_sum(const Workspace* w, const SrcgArgs& a, const GroupTotals& gt, int)
-{
-    hipLaunchKernelGGL(k_srcg_group_sum, dim3((a.nrhs + 63) / 64), dim3(64), 0, w->v.stream, a, gt);
-}
-
-// Every member's stream waits for what its neighbours' streams hold so far.
-// The prologue needs it once: a member's step overwrites the t rows its
-// neighbours' halos read, with no group sum between the two (in the loop the
-// sum is that fence: hpccg_group.h's argument for p, here for u).
-int neighbour_fence(const SrcgGroup& G)
-{
-    if (G.P == 1) return 0;
-    for (int r = 0; r < G.P; r++) {
-        TRY(use(G, r));
-        HIP_TRY(hipEventRecord(G.w[r]->evr, G.v[r].stream));
-    }
-    for (int r = 0; r < G.P; r++) {
-        TRY(use(G, r));
-        if (r > 0) HIP_TRY(hipStreamWaitEvent(G.v[r].stream, G.w[r - 1]->evr, 0));
-        if (r < G.P - 1) HIP_TRY(hipStreamWaitEvent(G.v[r].stream, G.w[r + 1]->evr, 0));
-    }
-    return 0;
-}
-
-// step, the halo of u, SpMM and finalize on every member, then the group's one sum.
-int group_iteration(const SrcgGroup& G, int nrhs, bool prologue, HaloLaunch halo, const GroupTotals& gt,
-                    const GroupLaunch<Workspace, SrcgArgs>& L)
-{
-    for (int r = 0; r < G.P; r++) {
-        TRY(use(G, r));
-        launch_step(G.w[r], G.a[r], prologue);
-    }
-    TRY(group_halo(G, nrhs, halo));
-    for (int r = 0; r < G.P; r++) {
-        TRY(use(G, r));
-        launch_spmm64<SrcgGroupUnit>(G.w[r], G.a[r], false);
-        launch_finalize(G.w[r], G.a[r]);
-    }
-    return group_sum(G, gt, kDotRR, L);
-}
-
-// The single-reduction CG over the group on the columns staged in the members'
-// b and x: hpccg_srcg.hip's launch sequence on every member's stream, the halo
-// after t and after every step, one sum after every finalize. Every
-// kCheckEvery iterations the host reads member 0's "columns ended" word, as
-// group_run_cg does.
-int group_run_srcg(const SrcgGroup& G, int nrhs, int max_iter, double tol, HaloLaunch halo, int* niters,
-                   double* normr, double* wall)
-{
-    const GroupTotals gt = group_totals(G);
-    GroupLaunch<Workspace, SrcgArgs> L{};  // (group_sum takes the sum's launcher from it)
-    L.sum = launch_group_sum;
-    TRY(use(G, 0));
-    HIP_TRY(hipEventRecord(G.w[0]->ev0, G.v[0].stream));
-    for (int r = 0; r < G.P; r++) {
-        TRY(use(G, r));
-        launch_init<SrcgGroupUnit>(G.w[r], G.a[r], max_iter, tol);
-        launch_t(G.w[r], G.a[r]);
-    }
-    TRY(group_halo(G, nrhs, halo));
-    TRY(neighbour_fence(G));
-    for (int r = 0; r < G.P; r++) {
-        TRY(use(G, r));
-        launch_spmm64<SrcgGroupUnit>(G.w[r], G.a[r], true);
-    }
-    TRY(group_iteration(G, nrhs, true, halo, gt, L));
-    HIP_TRY(hipGetLastError());
-    for (int k = 1; k < max_iter; k++) {
-        TRY(group_iteration(G, nrhs, false, halo, gt, L));
-        if (k % kCheckEvery == 0 && k + 1 < max_iter) {
-            bool ended = false;
-            TRY(group_ended(G, nrhs, &ended));
-            if (ended) break;
-        }
-    }
-    return group_finish(G, nrhs, niters, normr, wall);
+    const SrcgGroupLaunch<Workspace, SrcgArgs> S{launch_spmm64<SrcgGroupUnit>, p_buf, true};
+    return group_run_srcg<SrcgGroupUnit>(G, nrhs, max_iter, tol, halo, S, niters, normr, wall);
 }
 
 }  // namespace
@@ -289,7 +189,7 @@ int hpccg_hip_group_srcg_solve_device(hpccg_hip_matrix* const* Ms, int nranks, i
                                       double* normr, double* times)
 {
     return group_diag_solve_device<SrcgGroupUnit>(Ms, nranks, nrhs, B_dev, ldb, X_dev, ldx, minv_dev, max_iter,
-                                                  tolerance, niters, normr, times, group_run_srcg);
+                                                  tolerance, niters, normr, times, group_run);
 }
 
 int hpccg_hip_group_srcg_last_trace(hpccg_hip_matrix* const* Ms, int nranks, int col, double* out, int cap)

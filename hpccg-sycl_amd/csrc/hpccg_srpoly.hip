@@ -27,13 +27,16 @@
 // hpccg_poly_bodies.h; the finalize is hpccg_srcg_bodies.h. The host code is
 // hpccg_poly_host.h (the workspace's polynomial state, the step launchers, the
 // bound, the interval) over hpccg_onerank_host.h (the dispatch, the checks, the
-// preconditioner, the solve, the bookkeeping exports); the launch loop, in
-// hpccg_srcg.hip's shape, is this unit's. No kernel here waits on another
-// block.
+// preconditioner, the solve, the bookkeeping exports); the launch loop, its
+// frame, the launchers of t, the fused step and the finalize, and p and s are
+// hpccg_srcg_host.h, shared with hpccg_srcg.hip. This unit keeps its kernel
+// arguments, the d steps after the fused one and the SpMM of u. No kernel here
+// waits on another block.
 #include <hip/hip_runtime.h>
 
 #include "../../include/hpccg_hip_srpoly.h"
 #include "hpccg_poly_host.h"
+#include "hpccg_srcg_host.h"
 #include "hpccg_srpoly_bodies.h"
 
 #pragma clang fp contract(off)
@@ -128,19 +131,15 @@ __global__ __launch_bounds__(kBlock) void k_srpoly_bound_top(const double* __res
 }
 
 // ---------------------------------------------------------------------------
-// host: hpccg_poly_host.h over this unit's kernels, with its own launch loop
+// host: hpccg_poly_host.h and hpccg_srcg_host.h over this unit's kernels
 // ---------------------------------------------------------------------------
 // hpccg_poly_host.h's workspace with the recurrence's plain columns (w = A u is
 // the engine's Ap).
-struct Workspace : PolyWorkspace {
-    double *pd = nullptr, *sd = nullptr;  // p and s = A p (never zeroed again: k == 1 reads u and w)
-
+struct Workspace : PolyWorkspace, SrcgColumns {
     void free_own_vectors()
     {
         PolyWorkspace::free_own_vectors();
-        for (double* q : {pd, sd})
-            if (q) (void)hipFree(q);
-        pd = sd = nullptr;
+        free_ps();
     }
 };
 
@@ -152,6 +151,14 @@ struct Srpoly {
     static long long row0(const Workspace* w) { return w->v.guard_rows; }
 
     static constexpr auto init = k_srpoly_init;
+    template <int kR>
+    static constexpr auto t = k_srpoly_t<kR>;
+    // (degree 0: hpccg_srcg_bodies.h's step)
+    template <int kR>
+    static auto fused_step(const Workspace* w)
+    {
+        return w->degree > 0 ? k_srpoly_step<kR, true> : k_srpoly_step<kR, false>;
+    }
     // (prologue: no u.w partial, the SpMM of t)
     template <int kW, int kR, int kWaves>
     static constexpr auto spmm_a = k_srpoly_spmm_a<kW, kR, kWaves>;
@@ -161,23 +168,13 @@ struct Srpoly {
     static constexpr auto step = k_srpoly_cheb<kW, kR, kWaves>;
     template <int kR>
     static constexpr auto step_sell = k_srpoly_cheb_sell<kR>;
+    static constexpr auto finalize = k_srpoly_finalize;
     static constexpr auto diag = k_srpoly_diag;
     static constexpr auto check = k_srpoly_check;
     static constexpr auto q = k_srpoly_q;
     static constexpr auto bound = k_srpoly_bound;
     static constexpr auto bound_top = k_srpoly_bound_top;
 };
-
-// hpccg_poly_host.h's vectors and p and s, for ncols columns and a history of
-// max_iter + 1 entries per column.
-int ensure_srpoly_vectors(Workspace* w, int ncols, int max_iter)
-{
-    const size_t npad = (size_t)w->v.npad;
-    return ensure_vectors(w, ncols, max_iter, p_column(w->v), 0, [&](int cap) {
-        TRY(alloc_zero(w, &w->pd, npad * cap));
-        return alloc_zero(w, &w->sd, npad * cap);
-    });
-}
 
 SrpolyArgs make_srpoly_args(const Workspace* w, int nrhs, const double* m)
 {
@@ -189,101 +186,36 @@ SrpolyArgs make_srpoly_args(const Workspace* w, int nrhs, const double* m)
     return a;
 }
 
-void launch_t(const Workspace* w, const SrpolyArgs& a)
-{
-    // (prologue: col_p's form)
-    launch_chunks(w, a, true, [](auto r) { return k_srpoly_t<decltype(r)::value>; });
-}
-
 // The fused step, then steps 1 .. d: u = z_d ends in buffer d & 1 (degree 0: u = m r in p's buffer).
 void launch_step(const Workspace* w, const SrpolyArgs& a, bool prologue)
 {
-    const int d = w->degree;
-    launch_chunks(w, a, prologue, [d](auto r) {
-        return d > 0 ? k_srpoly_step<decltype(r)::value, true> : k_srpoly_step<decltype(r)::value, false>;
-    });
-    for (int j = 1; j <= d; j++) launch_step64<Srpoly>(w, step_args<Srpoly>(w, a, j));
+    launch_srcg_step<Srpoly>(w, a, prologue);
+    for (int j = 1; j <= w->degree; j++) launch_step64<Srpoly>(w, step_args<Srpoly>(w, a, j));
 }
 
 // w = A u and the u.w slice partial: the SpMM with u in p's place.
-void launch_spmm_u(const Workspace* w, SrpolyArgs a)
+void launch_spmm_u(const Workspace* w, SrpolyArgs a, bool prologue)
 {
     if (w->degree > 0) a.p = const_cast<double*>(a.u);
-    launch_spmm64<Srpoly>(w, a, false);
-}
-
-void launch_finalize(const Workspace* w, const SrpolyArgs& a)
-{
-    hipLaunchKernelGGL(k_srpoly_finalize, dim3(a.nrhs), dim3(kFinThreads), 0, w->v.stream, a, 0);
-}
-
-// One recurrence per column of the states on the device, on (b, x) of a: the
-// prologue (t, A t, r and u = P(r), A u, the three totals), then iterations
-// 1 .. kmax - 1 of step with its d steps, SpMM, finalize, launched eagerly on
-// the matrix's stream. Every kCheckEvery iterations the host reads the
-// "columns ended" word and stops launching once every column has ended.
-int run_iterations(Workspace* w, const SrpolyArgs& a, int nrhs, int kmax)
-{
-    hipStream_t s = w->v.stream;
-    launch_t(w, a);
-    launch_spmm64<Srpoly>(w, a, true);
-    launch_step(w, a, true);
-    launch_spmm_u(w, a);
-    launch_finalize(w, a);
-    HIP_TRY(hipGetLastError());
-    for (int k = 1; k < kmax; k++) {
-        launch_step(w, a, false);
-        launch_spmm_u(w, a);
-        launch_finalize(w, a);
-        if (k % kCheckEvery == 0 && k + 1 < kmax) {
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(w->h_ended, w->ended, sizeof(int), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            if (*w->h_ended >= nrhs) break;  // later launches would be no-ops for every column
-        }
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
+    launch_spmm64<Srpoly>(w, a, prologue);
 }
 
 // The recurrence on the columns staged in the workspace's b and x.
 int run_srpoly(Workspace* w, int nrhs, const double* m, int max_iter, double tol, int* niters, double* normr,
                double* wall)
 {
-    const SrpolyArgs a = make_srpoly_args(w, nrhs, m);
-    HIP_TRY(hipEventRecord(w->ev0, w->v.stream));
-    launch_init<Srpoly>(w, a, max_iter, tol);
-    TRY(run_iterations(w, a, nrhs, max_iter));
-    return finish_recurrence(w, nrhs, niters, normr, wall);
+    return run_srcg<Srpoly>(w, make_srpoly_args(w, nrhs, m), nrhs, max_iter, tol, niters, normr, wall, launch_step,
+                            launch_spmm_u);
 }
 
-// The solve: hpccg_onerank_host.h's, with hpccg_poly_host.h's checks of the
-// degree and the bounds before the matrix and its interval once m is in hand.
+// The solve: hpccg_poly_host.h's, with p and s beside its vectors and this unit's recurrence.
 int solve_srpoly(hpccg_hip_matrix* M, int nrhs, const double* B, long long ldb, double* X, long long ldx,
                  const double* minv, int degree, double lmin, double lmax, int max_iter, double tol, int* niters,
                  double* normr, double* times, bool host)
 {
-    const char* who = Srpoly::who;
-    return solve_onerank<Srpoly>(
-        M, nrhs, B, ldb, X, ldx, minv, max_iter, tol, niters, normr, times, host,
-        [&]() -> int {
-            if (degree < 0 || degree > kPolyMaxDegree)
-                return fail(HPCCG_HIP_EINVAL, "%s: degree %d (0 to %d)", who, degree, kPolyMaxDegree);
-            return check_bounds(who, lmin, lmax);
-        },
-        nullptr,
-        [&](Workspace* w, const double* m, int kmax) -> int {
-            TRY(resolve_interval(who, degree, &lmin, &lmax, &w->cheb0, w->aj, w->bj, [&](double* top) {
-                return minv ? compute_bound<Srpoly>(w, m, top) : jacobi_bound<Srpoly>(w, top);
-            }));
-            TRY(ensure_srpoly_vectors(w, nrhs, kmax));
-            w->degree = degree;
-            w->last_lmin = lmin;
-            w->last_lmax = lmax;
-            w->solved = true;
-            return 0;
-        },
-        run_srpoly);
+    return solve_common<Srpoly>(
+        M, nrhs, B, ldb, X, ldx, minv, degree, lmin, lmax, max_iter, tol, niters, normr, times, host, nullptr,
+        [](Workspace* w, int cap) { return alloc_ps(w, (size_t)w->v.npad * cap); }, run_srpoly);
 }
 
 }  // namespace

@@ -31,14 +31,19 @@
 // The group engine is hpccg_group.h; the members' preconditioner, the argument
 // checks and the staging are hpccg_group_host.h; the members' bound and the
 // polynomial's workspace, arguments, step launchers and interval are
-// hpccg_poly_group_host.h and hpccg_poly_host.h; this unit adds p and s, the
-// sum kernel, the launch loop (group_iteration: the ordering argument is written
-// there) and the body of solve_device. Ordering between the members is by
+// hpccg_poly_group_host.h and hpccg_poly_host.h, whose solve_device this unit
+// runs with p and s and its own recurrence; p and s, the launchers, the sum
+// kernel's body, the fence between neighbours and the launch loop
+// (group_iteration: the ordering argument is written there) are
+// hpccg_srcg_group_host.h (over hpccg_srcg_host.h), shared with
+// hpccg_srcg_group.hip. This unit keeps its kernel arguments, the steps
+// 1 .. d with their halos and the SpMM of u. Ordering between the members is by
 // stream events only. No kernel here waits on another block.
 #include <hip/hip_runtime.h>
 
 #include "../../include/hpccg_hip_srpoly_group.h"
 #include "hpccg_poly_group_host.h"
+#include "hpccg_srcg_group_host.h"
 #include "hpccg_srpoly_bodies.h"
 
 #pragma clang fp contract(off)
@@ -106,24 +111,10 @@ __global__ __launch_bounds__(kFinThreads) void k_srpoly_group_finalize(SrpolyArg
     srcg_finalize(a, store_total);
 }
 
-// The group's three dots and the column's state on every member: one thread
-// per column on member 0's stream, after every member's local finalize. Each
-// dot is the members' local totals added in rank order from 0.0; the column
-// advances once, as in the one-rank finalize, and its state is stored into
-// every member's state array, so all members freeze a column together. hist
-// and the "columns ended" word are member 0's (a: its args).
+// The group's three dots and the column's state on every member (hpccg_srcg_group_host.h).
 __global__ void k_srpoly_group_sum(SrpolyArgs a, GroupTotals g)
 {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= a.nrhs) return;
-    ColState s = a.st[c];
-    if (!s.run) return;  // frozen on every member
-    double rr = 0.0, gamma = 0.0, delta = 0.0;
-    for (int r = 0; r < g.nranks; r++) rr += g.tot[r][(size_t)kDotRR * g.cap[r] + c];
-    for (int r = 0; r < g.nranks; r++) gamma += g.tot[r][(size_t)kDotRZ * g.cap[r] + c];
-    for (int r = 0; r < g.nranks; r++) delta += g.tot[r][(size_t)kDotPAP * g.cap[r] + c];
-    srcg_advance(a, &s, c, rr, gamma, delta);
-    for (int r = 0; r < g.nranks; r++) g.st[r][c] = s;
+    srcg_group_sum(a, g);
 }
 
 // The halo of every column of one guarded buffer in one launch per member (hpccg_group.h).
@@ -168,15 +159,11 @@ __global__ __launch_bounds__(kBlock) void k_srpoly_group_bound_top(const double*
 // z buffers, the cached 1 / a_ii with its verdict and the member's part of
 // Jacobi's bound, a slot for a caller's m, the bound's vectors) with the
 // member's events and p0, and the recurrence's plain columns p and s.
-struct Workspace : PolyWorkspace, GroupMember {
-    double *pd = nullptr, *sd = nullptr;  // p and s = A p (never zeroed again: k == 1 reads u and w)
-
+struct Workspace : PolyWorkspace, GroupMember, SrcgColumns {
     void free_own_vectors()
     {
         PolyWorkspace::free_own_vectors();
-        for (double* q : {pd, sd})
-            if (q) (void)hipFree(q);
-        pd = sd = nullptr;
+        free_ps();
     }
     void free_own_rest()
     {
@@ -196,6 +183,14 @@ struct GroupSrpoly {
     static int image(Workspace*, int) { return 0; }  // (the fp64 image the matrix holds)
 
     static constexpr auto init = k_srpoly_group_init;
+    template <int kR>
+    static constexpr auto t = k_srpoly_group_t<kR>;
+    // (degree 0: hpccg_srcg_bodies.h's step)
+    template <int kR>
+    static auto fused_step(const Workspace* w)
+    {
+        return w->degree > 0 ? k_srpoly_group_step<kR, true> : k_srpoly_group_step<kR, false>;
+    }
     template <int kW, int kR, int kWaves>
     static constexpr auto spmm_a = k_srpoly_group_spmm_a<kW, kR, kWaves>;
     template <int kR>
@@ -204,6 +199,8 @@ struct GroupSrpoly {
     static constexpr auto step = k_srpoly_group_cheb<kW, kR, kWaves>;
     template <int kR>
     static constexpr auto step_sell = k_srpoly_group_cheb_sell<kR>;
+    static constexpr auto finalize = k_srpoly_group_finalize;
+    static constexpr auto sum = k_srpoly_group_sum;
     static constexpr auto halo = k_srpoly_group_halo;
     static constexpr auto diag = k_srpoly_group_diag;
     static constexpr auto check = k_srpoly_group_check;
@@ -230,95 +227,16 @@ SrpolyArgs make_member_args(const Workspace* w, int nrhs, const double* m)
     return a;
 }
 
-void launch_t(const Workspace* w, const SrpolyArgs& a)
-{
-    // (prologue: col_p's form)
-    launch_chunks(w, a, true, [](auto r) { return k_srpoly_group_t<decltype(r)::value>; });
-}
-
-void launch_step(const Workspace* w, const SrpolyArgs& a, bool prologue)
-{
-    const int d = w->degree;
-    launch_chunks(w, a, prologue, [d](auto r) {
-        return d > 0 ? k_srpoly_group_step<decltype(r)::value, true> : k_srpoly_group_step<decltype(r)::value, false>;
-    });
-}
-
 // w = A u and the u.w slice partial: the SpMM with u in p's place.
-void launch_spmm_u(const Workspace* w, SrpolyArgs a)
+void launch_spmm_u(const Workspace* w, SrpolyArgs a, bool prologue)
 {
     if (w->degree > 0) a.p = const_cast<double*>(a.u);
-    launch_spmm64<GroupSrpoly>(w, a, false);
+    launch_spmm64<GroupSrpoly>(w, a, prologue);
 }
 
-// (store_total: always 1 here, a member's part; the state is the group sum's)
-void launch_finalize(const Workspace* w, const SrpolyArgs& a)
+// Steps 1 .. d over the group, each after the halo of the buffer it reads (halos 0 .. d - 1 of group_iteration).
+int group_steps(const Grp& G, int nrhs, HaloLaunch halo)
 {
-    hipLaunchKernelGGL(k_srpoly_group_finalize, dim3(a.nrhs), dim3(kFinThreads), 0, w->v.stream, a, 1);
-}
-
-// (which: group_sum's; the one launch sums all three dots)
-void launch_sum(const Workspace* w, const SrpolyArgs& a, const GroupTotals& gt, int)
-{
-    hipLaunchKernelGGL(k_srpoly_group_sum, dim3((a.nrhs + 63) / 64), dim3(64), 0, w->v.stream, a, gt);
-}
-
-// Every member's stream waits for what its neighbours' streams hold so far.
-// Degree 0's prologue needs it once: a member's step overwrites the t rows (u
-// shares p's buffer there) its neighbours' halos read, with no group sum
-// between the two. With d >= 1 nothing stores p's buffer after t.
-int neighbour_fence(const Grp& G)
-{
-    if (G.P == 1) return 0;
-    for (int r = 0; r < G.P; r++) {
-        TRY(use(G, r));
-        HIP_TRY(hipEventRecord(G.w[r]->evr, G.v[r].stream));
-    }
-    for (int r = 0; r < G.P; r++) {
-        TRY(use(G, r));
-        if (r > 0) HIP_TRY(hipStreamWaitEvent(G.v[r].stream, G.w[r - 1]->evr, 0));
-        if (r < G.P - 1) HIP_TRY(hipStreamWaitEvent(G.v[r].stream, G.w[r + 1]->evr, 0));
-    }
-    return 0;
-}
-
-// ---------------------------------------------------------------------------
-// One iteration: every member's fused step (step 0 into buffer 0), then for
-// j = 1 .. d the halo of z buffer (j - 1) & 1 and every member's step j, which
-// stores the member's own rows of buffer j & 1; then the halo of u = z_d
-// (buffer d & 1; degree 0: of p's buffer), every member's SpMM and finalize,
-// and the group's one sum. Call the halo that follows step j halo j
-// (j = 0 .. d; it moves buffer j & 1): d + 1 halos per iteration.
-//
-// Two buffers suffice, and no member's rows of a buffer are overwritten before
-// every neighbour has pulled them:
-//   - Halos 0 .. d - 1 and steps 1 .. d are hpccg_poly_group_host.h's
-//     (group_poly_update): member r's halo j waits on the events its neighbours
-//     record after their step j; the next store into those rows within the
-//     iteration is the neighbour's step j + 2, which follows its halo j + 1,
-//     which waits on r's event recorded after r's step j + 1, which follows r's
-//     halo j on r's stream.
-//   - Halo d moves u after step d. Nothing of this iteration stores buffer
-//     d & 1 after step d: the SpMM and the finalize read only.
-//   - The next iteration's fused step stores buffer 0 on every member, and its
-//     step 1 buffer 1. Both follow the group's sum on every stream; the sum
-//     waits for every member's finalize; every member's finalize follows all
-//     its halos, halo d included, on its own stream. So every pull of either
-//     buffer is over before the next iteration stores into it.
-//   - The fused step reads the member's own rows of u = z_d before it stores
-//     buffer 0 (for an even d the same rows, by the same thread); it follows
-//     the member's SpMM, the last reader of u's ghost planes, on its stream.
-//   - A member's ghost planes are stored by its halos and read by its steps and
-//     its SpMM only, all on its stream.
-// Frozen columns' planes move too; a frozen column's z is no longer stored.
-// ---------------------------------------------------------------------------
-int group_iteration(const Grp& G, int nrhs, bool prologue, HaloLaunch halo, const GroupTotals& gt,
-                    const GroupLaunch<Workspace, SrpolyArgs>& L)
-{
-    for (int r = 0; r < G.P; r++) {
-        TRY(use(G, r));
-        launch_step(G.w[r], G.a[r], prologue);
-    }
     const int d = G.w[0]->degree;
     for (int j = 1; j <= d; j++) {
         const int in = (j - 1) & 1;
@@ -328,99 +246,18 @@ int group_iteration(const Grp& G, int nrhs, bool prologue, HaloLaunch halo, cons
             launch_step64<GroupSrpoly>(G.w[r], step_args<GroupSrpoly>(G.w[r], G.a[r], j));
         }
     }
-    TRY(group_halo_of(G, nrhs, halo, [&](int r) { return u_buf(G, r); }));
-    for (int r = 0; r < G.P; r++) {
-        TRY(use(G, r));
-        launch_spmm_u(G.w[r], G.a[r]);
-        launch_finalize(G.w[r], G.a[r]);
-    }
-    return group_sum(G, gt, kDotRR, L);
+    return 0;
 }
 
-// The recurrence over the group on the columns staged in the members' b and x:
-// hpccg_srpoly.hip's launch sequence on every member's stream. Every
-// kCheckEvery iterations the host reads member 0's "columns ended" word, as
-// group_run_cg does.
-int group_run_srpoly(const Grp& G, int nrhs, int max_iter, double tol, HaloLaunch halo, int* niters, double* normr,
-                     double* wall)
+// The launch loop with u = z_d: the prologue fences at degree 0 only, where u shares p's buffer with t.
+int group_run(const Grp& G, int nrhs, int max_iter, double tol, HaloLaunch halo, int* niters, double* normr,
+              double* wall)
 {
-    const GroupTotals gt = group_totals(G);
-    GroupLaunch<Workspace, SrpolyArgs> L{};  // (group_sum takes the sum's launcher from it)
-    L.sum = launch_sum;
-    TRY(use(G, 0));
-    HIP_TRY(hipEventRecord(G.w[0]->ev0, G.v[0].stream));
-    for (int r = 0; r < G.P; r++) {
-        TRY(use(G, r));
-        launch_init<GroupSrpoly>(G.w[r], G.a[r], max_iter, tol);
-        launch_t(G.w[r], G.a[r]);
-    }
-    TRY(group_halo(G, nrhs, halo));
-    if (G.w[0]->degree == 0) TRY(neighbour_fence(G));
-    for (int r = 0; r < G.P; r++) {
-        TRY(use(G, r));
-        launch_spmm64<GroupSrpoly>(G.w[r], G.a[r], true);
-    }
-    TRY(group_iteration(G, nrhs, true, halo, gt, L));
-    HIP_TRY(hipGetLastError());
-    for (int k = 1; k < max_iter; k++) {
-        TRY(group_iteration(G, nrhs, false, halo, gt, L));
-        if (k % kCheckEvery == 0 && k + 1 < max_iter) {
-            bool ended = false;
-            TRY(group_ended(G, nrhs, &ended));
-            if (ended) break;
-        }
-    }
-    return group_finish(G, nrhs, niters, normr, wall);
+    const SrcgGroupLaunch<Workspace, SrpolyArgs> S{launch_spmm_u, u_buf, G.w[0]->degree == 0, group_steps};
+    return group_run_srcg<GroupSrpoly>(G, nrhs, max_iter, tol, halo, S, niters, normr, wall);
 }
 
-// hpccg_poly_group_host.h's solve_device (the degree and the bounds checked
-// after the arrays, the interval resolved once every member's m is in hand)
-// with this unit's vectors and launch loop.
-int solve_device(hpccg_hip_matrix* const* Ms, int nranks, int nrhs, const double* const* B_dev, const long long* ldb,
-                 double* const* X_dev, const long long* ldx, const double* const* minv_dev, int degree, double lmin,
-                 double lmax, int max_iter, double tolerance, int* niters, double* normr, double* times)
-{
-    using U = GroupSrpoly;
-    const char* who = U::who;
-    return group_solve_device<U>(
-        Ms, nranks, nrhs, B_dev, ldb, X_dev, ldx, minv_dev, max_iter, niters, normr, times, true,
-        [&]() -> int {
-            if (degree < 0 || degree > kPolyMaxDegree)
-                return fail(HPCCG_HIP_EINVAL, "%s: degree %d (0 to %d)", who, degree, kPolyMaxDegree);
-            return check_bounds(who, lmin, lmax);
-        },
-        [&](Grp& G, int kmax) -> int {
-            const HaloLaunch halo = halo_launcher<U>();
-            // the preconditioner and the interval first, on every member: a
-            // refused call leaves every X as it is
-            std::vector<const double*> m;
-            TRY(group_preconditioner<U>(Ms, &G, minv_dev, &m));
-            double cheb0 = 0.0, aj[kPolyMaxDegree + 1] = {}, bj[kPolyMaxDegree + 1] = {};
-            TRY(resolve_interval(who, degree, &lmin, &lmax, &cheb0, aj, bj, [&](double* top) {
-                return minv_dev ? compute_group_bound<U>(G, m, halo, nullptr, top)
-                                : jacobi_group_bound<U>(G, m, halo, top);
-            }));
-            for (int r = 0; r < G.P; r++) {
-                Workspace* w = G.w[r];
-                const size_t npad = (size_t)w->v.npad;
-                TRY(ensure_vectors(w, nrhs, kmax, guarded_p_column(w->v).pcs, 3, [&](int cap) {
-                    TRY(alloc_zero(w, &w->pd, npad * cap));
-                    return alloc_zero(w, &w->sd, npad * cap);
-                }));
-                w->degree = degree;
-                w->cheb0 = cheb0;
-                std::copy(aj, aj + kPolyMaxDegree + 1, w->aj);
-                std::copy(bj, bj + kPolyMaxDegree + 1, w->bj);
-                G.a[r] = make_member_args(w, nrhs, m[r]);
-            }
-            G.w[0]->last_lmin = lmin;
-            G.w[0]->last_lmax = lmax;
-            G.w[0]->solved = true;
-            return group_run_staged(G, nrhs, B_dev, ldb, X_dev, ldx, times, [&](double* wall) {
-                return group_run_srpoly(G, nrhs, kmax, tolerance, halo, niters, normr, wall);
-            });
-        });
-}
+int more_vectors(Workspace* w, int cap) { return alloc_ps(w, (size_t)w->v.npad * cap); }
 
 }  // namespace
 
@@ -437,8 +274,9 @@ int hpccg_hip_group_srpoly_solve_device(hpccg_hip_matrix* const* Ms, int nranks,
                                         const double* const* minv_dev, int degree, double lmin, double lmax,
                                         int max_iter, double tolerance, int* niters, double* normr, double* times)
 {
-    return solve_device(Ms, nranks, nrhs, B_dev, ldb, X_dev, ldx, minv_dev, degree, lmin, lmax, max_iter, tolerance,
-                        niters, normr, times);
+    return group_poly_solve_device<GroupSrpoly>(Ms, nranks, nrhs, B_dev, ldb, X_dev, ldx, minv_dev, degree, lmin, lmax,
+                                                max_iter, tolerance, niters, normr, times, more_vectors,
+                                                make_member_args, group_run);
 }
 
 int hpccg_hip_group_srpoly_bound(hpccg_hip_matrix* const* Ms, int nranks, const double* const* minv_dev, double* lmax)

@@ -16,7 +16,7 @@ EINVAL = -1
 
 # library -> (message prefix, whether solve_device takes degree, lmin, lmax)
 UNITS = {"pcg_group": ("group pcg", False), "srcg_group": ("group srcg", False), "poly_group": ("group poly", True),
-         "poly32_group": ("group poly32", True)}
+         "poly32_group": ("group poly32", True), "srpoly_group": ("group srpoly", True)}
 POLY = [u for u, (_, poly) in UNITS.items() if poly]
 
 buf = (C.c_double * 8)()

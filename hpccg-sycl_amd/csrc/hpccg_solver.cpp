@@ -2,422 +2,15 @@
 // SELL-512 / SELL-512-A conversion, device residency, the device-resident CG
 // driver (HPCCG.cpp:312-402) replayed from hipGraphs, the z-slab halo exchange
 // and scalar all-reduces over RCCL (exchange_externals.cpp:51-131,
-// ddot.cpp:75-85), the in-process rank group, and the C ABI.
-#include <dlfcn.h>
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-
-#include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <climits>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <iostream>
-#include <map>
-#include <mutex>
-#include <string>
-#include <system_error>
-#include <thread>
-#include <unordered_map>
-#include <vector>
-
-#include "../../include/HPC_Sparse_Matrix.hpp"
-#include "../../include/hpccg_hip.h"
-#include "hpccg_internal.h"
+// ddot.cpp:75-85), the in-process rank group, and their part of the C ABI.
+// The communicator, the device-free plans, the option tables, the diagnostics
+// and the drop-in cache are units of their own (hpccg_host.h lists them).
+#include "hpccg_host.h"
 
 using namespace hpccg;
 
-// ---------------------------------------------------------------------------
-// errors
-// ---------------------------------------------------------------------------
-namespace {
-
-thread_local std::string g_err;
-
-int set_err(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-}  // namespace
-
-namespace hpccg {
-// error channel for the other host translation units (read_hpc_row.cpp)
-int set_error_message(int code, const char* msg) { return set_err(code, "%s", msg); }
-}  // namespace hpccg
-
-namespace {
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return set_err(e_ == hipErrorOutOfMemory ? HPCCG_HIP_ENOMEM : HPCCG_HIP_EHIP,          \
-                           "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);   \
-    } while (0)
-
-#define NCCL_TRY(expr)                                                                             \
-    do {                                                                                           \
-        ncclResult_t r_ = (expr);                                                                  \
-        if (r_ != ncclSuccess)                                                                     \
-            return set_err(HPCCG_HIP_ERCCL, "%s: %s (%s:%d)", #expr, ncclGetErrorString(r_),      \
-                           __FILE__, __LINE__);                                                    \
-    } while (0)
-
-#define TRY(expr)                                                                                  \
-    do {                                                                                           \
-        int rc_ = (expr);                                                                          \
-        if (rc_ != 0) return rc_;                                                                  \
-    } while (0)
-
-// ---------------------------------------------------------------------------
-// communicator (one rank per GPU per process)
-// ---------------------------------------------------------------------------
-struct Comm {
-    ncclComm_t comm = nullptr;
-    int nranks = 1;
-    int rank = 0;
-    // host-bootstrapped (hpccg_hip_comm_init_host): no RCCL communicator; the
-    // setup exchanges go through the caller's all-gather, and the iteration
-    // must run without a collective (peer all-reduce + halo pull)
-    hpccg_hip_allgather_fn ag = nullptr;
-    void* ag_ctx = nullptr;
-    // RCCL: the setup collectives' stream and staging buffer
-    hipStream_t stream = nullptr;
-    unsigned char* d_buf = nullptr;
-    size_t buf_bytes = 0;
-};
-Comm g_comm;
-bool comm_host() { return g_comm.ag != nullptr; }
-bool comm_up() { return g_comm.comm != nullptr || g_comm.ag != nullptr; }
-
-void comm_reset()
-{
-    if (g_comm.comm) ncclCommDestroy(g_comm.comm);
-    if (g_comm.d_buf) (void)hipFree(g_comm.d_buf);
-    if (g_comm.stream) (void)hipStreamDestroy(g_comm.stream);
-    g_comm = Comm();
-}
-
-// All-gather of `bytes` host bytes per rank into all[nranks * bytes] (rank
-// order): RCCL staged through device memory, or the host bootstrap's
-// callback. The setup-time exchanges of make_local_matrix.cpp:185-201 /
-// :286-587 and the self-tests' verdicts go through here.
-int comm_allgather(const void* mine, void* all, size_t bytes)
-{
-    if (g_comm.nranks == 1 || !comm_up()) {
-        std::memcpy(all, mine, bytes);
-        return 0;
-    }
-    if (g_comm.ag) {
-        if (g_comm.ag(mine, all, (unsigned long long)bytes, g_comm.ag_ctx) != 0)
-            return set_err(HPCCG_HIP_EINVAL, "the host all-gather callback failed (%zu B per rank)", bytes);
-        return 0;
-    }
-    const size_t need = bytes * (size_t)(g_comm.nranks + 1);
-    if (!g_comm.stream) HIP_TRY(hipStreamCreateWithFlags(&g_comm.stream, hipStreamNonBlocking));
-    if (need > g_comm.buf_bytes) {
-        if (g_comm.d_buf) (void)hipFree(g_comm.d_buf);
-        g_comm.d_buf = nullptr;
-        g_comm.buf_bytes = 0;
-        HIP_TRY(hipMalloc(&g_comm.d_buf, need));
-        g_comm.buf_bytes = need;
-    }
-    unsigned char* d = g_comm.d_buf;
-    HIP_TRY(hipMemcpyAsync(d + bytes * g_comm.nranks, mine, bytes, hipMemcpyHostToDevice, g_comm.stream));
-    NCCL_TRY(ncclAllGather(d + bytes * g_comm.nranks, d, bytes, ncclUint8, g_comm.comm, g_comm.stream));
-    HIP_TRY(hipStreamSynchronize(g_comm.stream));
-    HIP_TRY(hipMemcpy(all, d, bytes * g_comm.nranks, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// Minimum over the ranks of one int (the self-tests' verdicts).
-int comm_min(int v, int* out)
-{
-    std::vector<int> all(std::max(1, g_comm.nranks));
-    TRY(comm_allgather(&v, all.data(), sizeof v));
-    *out = *std::min_element(all.begin(), all.end());
-    return 0;
-}
-
-// The job's in-kernel transport verdicts from every rank's own self-test
-// results (collective; hpccg_hip_transport_verdict): local = {peer all-reduce,
-// halo pull, production protocol} as this rank saw them. The peer all-reduce
-// and the pull each stay on only where every rank passed; the protocol test
-// counts only where both did, and a protocol failure on any rank turns both
-// off on every rank (RCCL then carries the scalars and r's planes). Every
-// rank computes the same three values from the same gathered table.
-int transport_verdict(const int local[3], int out[3])
-{
-    TRY(comm_min(local[0] ? 1 : 0, &out[0]));
-    TRY(comm_min(local[1] ? 1 : 0, &out[1]));
-    TRY(comm_min((out[0] && out[1] && local[2]) ? 1 : 0, &out[2]));
-    if (out[0] && out[1] && !out[2]) out[0] = out[1] = 0;
-    return 0;
-}
-
-// Gather halo plan (make_local_matrix.cpp:58-610, exchange_externals.cpp:51-131)
-// for partitions the z-slab plan cannot serve: the external columns get local
-// indices n, n+1, ... grouped by owning rank, groups in order of first
-// appearance and first appearance inside a group, exactly as
-// make_local_matrix.cpp:96-200 numbers them.
-struct GatherPlan {
-    std::vector<long long> ext_global;              // external j <-> local column n + j
-    std::unordered_map<long long, int> ext_of;      // global column -> j
-    std::vector<int> recv_rank, recv_off, recv_cnt; // externals owned by recv_rank[i]: [off, off + cnt)
-    std::vector<std::vector<int>> req;              // per owner: the global columns we need, our order
-    std::vector<int> send_rank, send_off, send_cnt; // per requester: a run of send_idx
-    std::vector<int> send_idx;                      // local rows packed for the requesters
-};
-
-// In-process rank group (hpccg_hip_group_*): while a group member is being
-// created on this thread, rank/size come from here instead of the RCCL
-// communicator, and the halo plan is made by hpccg_hip_group_* afterwards.
-struct GroupCtx {
-    int active = 0, nranks = 1, rank = 0;
-    const int* info = nullptr;        // every member's {nrow, ghost_lo, ghost_hi, start_row}, or null
-    const GatherPlan* plan = nullptr; // this member's gather plan (gather mode), or null
-};
-thread_local GroupCtx g_group_ctx;
-int g_halo_mode = 0;  // 0 auto (slab when it serves every rank), 1 slab only, 2 gather
-int g_keep_sell = 0;  // keep the SELL-512 image beside SELL-512-A (kernel A/B, diagnostics)
-// placement probe at creation: -1 auto (images over kPlaceMinBytes), 0 off, n
-// candidates. Off by default since round 4: the probe's gain is
-// box-dependent and it is asked for explicitly (bench.py --placement).
-int g_place_tries = 0;
-constexpr int kPlaceAuto = 6;        // candidates of the automatic probe
-constexpr int kPlacePhases = 4;      // values, p ring, r, Ap
-constexpr double kPlaceMinBytes = 512e6;  // auto: only images that stream from HBM
-int comm_nranks() { return g_group_ctx.active ? g_group_ctx.nranks : g_comm.nranks; }
-int comm_rank() { return g_group_ctx.active ? g_group_ctx.rank : g_comm.rank; }
-
-// ---------------------------------------------------------------------------
-// SELL-512 build from any row accessor. Entry order per row is preserved.
-// ---------------------------------------------------------------------------
-// Column map of the slab plan: global column -> index into [ghost_lo | n | ghost_hi].
-struct SlabCols {
-    long long col_base, ncol_ext;
-    long long operator()(long long c) const
-    {
-        const long long lc = c - col_base;
-        return (lc < 0 || lc >= ncol_ext) ? -1 : lc;
-    }
-};
-
-template <class RowLen, class RowAt, class ColMap>
-long long sell_build_impl(int nrow, ColMap colmap, RowLen row_len, RowAt row_at, unsigned int* slice_base,
-                          int* sell_cols, double* sell_vals, int uniform_width, int* err)
-{
-    const int nslices = (nrow + kSliceRows - 1) / kSliceRows;
-    long long total = 0;
-    int wmax = 0;
-    std::vector<int> w(nslices, 0);
-    for (int s = 0; s < nslices; s++) {
-        int m = 0;
-        for (int i = s * kSliceRows; i < std::min(nrow, (s + 1) * kSliceRows); i++) m = std::max(m, row_len(i));
-        w[s] = m;
-        wmax = std::max(wmax, m);
-    }
-    if (uniform_width) std::fill(w.begin(), w.end(), wmax);
-    for (int s = 0; s < nslices; s++) {
-        if (slice_base) slice_base[s] = (unsigned int)total;
-        total += w[s];
-    }
-    if (slice_base) slice_base[nslices] = (unsigned int)total;
-    if (!sell_cols || !sell_vals) return total * kSliceRows;
-    std::atomic<int> bad{0};
-    const int nth = std::max(1, std::min<int>(16, (int)std::thread::hardware_concurrency()));
-    auto work = [&](int t) {
-        for (int s = t; s < nslices; s += nth) {
-            const size_t b0 = (size_t)slice_base[s] * kSliceRows;
-            for (int lane = 0; lane < kSliceRows; lane++) {
-                const int i = s * kSliceRows + lane;
-                const int len = i < nrow ? row_len(i) : 0;
-                for (int j = 0; j < w[s]; j++) {
-                    const size_t e = b0 + (size_t)j * kSliceRows + lane;
-                    if (j < len) {
-                        double v;
-                        long long c;
-                        row_at(i, j, &c, &v);
-                        const long long lc = colmap(c);
-                        if (lc < 0) bad.store(1);
-                        sell_cols[e] = (int)lc;
-                        sell_vals[e] = v;
-                    } else {
-                        sell_cols[e] = -1;
-                        sell_vals[e] = 0.0;
-                    }
-                }
-            }
-        }
-    };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nth; t++) th.emplace_back(work, t);
-    work(0);
-    for (auto& x : th) x.join();
-    if (err) *err = bad.load();
-    return total * kSliceRows;
-}
-
-}  // namespace
-
-// ---------------------------------------------------------------------------
-// device matrix + CG workspace
-// ---------------------------------------------------------------------------
-struct hpccg_hip_matrix {
-    int device = 0;
-    int rank = 0, nranks = 1;  // z-slab rank of this matrix (RCCL communicator or in-process group)
-    int in_group = 0;          // 1: halo / all-reduce by hpccg_hip_group_solve, not RCCL
-    unsigned long long group_id = 0;  // the in-process group this member was made in (0: none)
-    int nrow = 0, start_row = 0, total_nrow = 0;
-    int ghost_lo = 0, ghost_hi = 0;
-    int send_lo = 0;  // rows to send to rank-1 (its ghost_hi)
-    int send_hi = 0;  // rows to send to rank+1 (its ghost_lo)
-    // gather plan (partitions the slab plan cannot serve): externals after the
-    // local rows (ghost_lo = 0, ghost_hi = number of externals)
-    int general = 0;
-    std::vector<int> recv_rank, recv_off, recv_cnt, send_rank, send_off, send_cnt;
-    int nsend = 0;
-    int* d_send_idx = nullptr;
-    double* d_send_buf = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_flush = nullptr;  // flush_stream's marker (default flags: system-scope release)
-    hipEvent_t ev_mid = nullptr;    // wait_matrix: blocking-sync marker before a solve's last graph chunk
-    int mid_pending = 0;            // ev_mid was recorded for the solve in flight
-    long long nnz = 0, nslots = 0;
-    int nslices = 0, grid = 0, width = 0, uniform = 0;
-    int kernel = 0;       // SpMV kernel in use (SpmvKernel)
-    int kernel_opt = -1;  // option spmv_kernel (-1 auto)
-    int use_graph = 1;
-    int fuse_p = -1;      // -1 auto: on where the kernel forms p_k itself
-    int fuse_update = -1; // the update as trailing blocks of the SpMV launch; -1 auto (fuse_update_effective)
-    int resident_update = -1;     // the resident pair kernels (k_spmv_ar, k_cg_persist; resident_of, persist_ok)
-    int nt_opt = -1;              // option nt (diagnostics): -1 auto (image_big), 0 / 1 force the matrix loads' hint
-    int resident_retries = 0;     // solves re-run after a resident launch's wait expired (resident_retry)
-    int resident_failed = 0;      // a resident launch's wait expired (GPU shared): the unit + update launch from then on
-    int resident_used = 0;        // the last solve ran k_spmv_ar
-    int last_dev_err = 0;         // the device error code the last failed solve recorded (DevError)
-    int last_dev_err_all = 0;     // ... its maximum over a job's ranks (all-reduced: the same on every rank)
-    size_t npartial = 0;  // dot slots (the last one: the fused update's p.Ap total)
-    int a2_ring = kA2RingDefault;  // pair kernel: LDS-DMA value ring depth per wave (0: register loads; uniform widths 27 and 7)
-    int fold = -1;        // -1 auto: 1 (both dots completed in their producers); 0 k_finalize
-    int force_comm = 0;   // diagnostics: 1 scalars through the RCCL communicator even at one rank;
-                          // 2 also the multi-rank iteration with a self send/recv as its halo
-    // SELL-512 (the general kernel; freed once SELL-512-A exists unless kept)
-    int has_sell = 0;
-    unsigned int* d_slice_base = nullptr;
-    int* d_cols = nullptr;
-    double* d_vals = nullptr;
-    // SELL-512-A
-    int has_a = 0, a_width = 0;
-    int a_reject = 0;  // SELL-512-A not built (diagnostics): 2 its flag read late, 3 rejected although
-                       // the device's columns fit (a kernel fault), 4 rejected and they do not
-    long long a_slots = 0;
-    double* d_aval = nullptr;
-    int* d_aoff = nullptr;
-    unsigned int* d_abase = nullptr;
-    int has_pairs = 0, alds2_doubles = 0;
-    int *d_alds2 = nullptr, *d_awin2 = nullptr, *d_awn2 = nullptr, *d_adiag2 = nullptr;
-    unsigned char* d_atri = nullptr;  // direct kernel: slices in the width's triple plan
-    // workspace (padded to a multiple of kSliceRows rows)
-    size_t npad = 0;
-    double* d_pbuf = nullptr;  // ring_alloc buffers of [guard | ghost_lo_pad | npad | ghost_hi_pad | guard]
-    int ring_alloc = 0;
-    double* d_p = nullptr;     // local rows of ring buffer 0
-    long long pstride = 0;
-    double* d_ahist = nullptr;
-    double* d_pslots = nullptr;   // persistent CG (persist_of): per-iteration dot slots
-    long long pslots_cap = 0;     // doubles
-    int x_defer = 2;      // deferred x: beside the SpMV where the kernel carries it, else batched (x_defer_effective)
-    int x_ring = -1;
-    double *d_r = nullptr, *d_Ap = nullptr, *d_x = nullptr, *d_b = nullptr;
-    double* d_rbuf = nullptr;
-    double* d_partial = nullptr;  // inside the d_kst block (not freed on its own)
-    double* d_scal = nullptr;  // g[2], loc[2], spare
-    double** d_gtab = nullptr;  // group fold (last member): the members' loc, then their g
-    std::vector<double*> h_gtab;
-    PullSeg* d_pseg = nullptr;  // group fold (member 0): every member's pull, done by its update
-    std::vector<PullSeg> h_pseg;
-    int gfold_used = 0;         // the last group solve summed its dots in the last member's kernels
-    int* d_kst = nullptr;      // [0, kErrBase) iteration state, then the device error record (kErrWords)
-    long long spin_us = kSpinTicksDefault / 100;  // bound of every in-kernel wait (option spin_budget_us)
-    int dbg_withhold = 0;      // debug: slice + 1 whose p.Ap partial is withheld (guard test)
-    int dbg_resident_stall = 0;  // debug: the resident launch's p.Ap wait expires (the retry test)
-    unsigned long long* d_tl = nullptr;  // diagnostics (dbg_timeline): per unit kTlWords block stamps
-    int tl_units = 0;
-    int solve_dirty = 0;       // a solve started and did not finish cleanly: reset the dot slots first
-    // peer-memory all-reduce of the CG scalars (option peer_allreduce)
-    int peer_ar = -1;                  // option peer_allreduce: -1 auto (peer_ar_of), 0 off, 1 on
-    int peer_auto_ok = 0;              // auto: the creation-time self-test passed on every rank
-    // r-halo by pull (option halo_pull: -1 auto, 0 the RCCL / peer-copy planes, 1 k_pull, 2 in-launch)
-    int halo_pull = -1;
-    int pull_auto_ok = 0;              // RCCL job: the creation-time pull test passed on every rank
-    int proto_auto_ok = 0;             // ... and the production-protocol test (protocol_autotest)
-    int persist_auto_ok = 0;           // ... and its persistent-launch run (every rank's blocks co-resident, same bits)
-    std::string selftest_note;         // why a creation-time self-test failed on this rank (diagnostics)
-    double* d_pull_lo = nullptr;       // rank - 1's r (its local row 0), mapped here (RCCL job)
-    double* d_pull_hi = nullptr;       // rank + 1's r
-    double* d_pullx_lo = nullptr;      // rank - 1's x workspace (d_x, its local row 0): the prologue's p = x halo
-    double* d_pullx_hi = nullptr;      // rank + 1's x
-    int pull_lo_n = 0;                 // rank - 1's row count
-    std::vector<void*> ipc_r_opened;   // the neighbours' r buffers mapped from other processes
-    double* d_mbox = nullptr;          // this rank's mailbox (kMboxSlots, uncached / fine-grained)
-    double** d_peers = nullptr;        // device table: every rank's mailbox, as this rank addresses it
-    int peers_for = 0;                 // ranks the table was built for (0: none)
-    std::vector<void*> ipc_opened;     // peers' mailboxes mapped from other processes
-    double* d_hist = nullptr;
-    unsigned long long* d_stamps = nullptr;
-    double* d_emul = nullptr;  // force_comm 2: self-exchange receive buffer (two planes)
-    int emul_plane = 0;        // force_comm 2: rows per plane (the largest column offset; 0 unknown)
-    int hist_cap = 0;
-    long long stamp_cap = 0;
-    // pinned readback of a solve's results (state, scalars, r.r history, timer
-    // stamps): one batch of async copies and one wait per solve
-    char* h_rb = nullptr;
-    size_t h_rb_bytes = 0;
-    std::vector<void*> graveyard;  // diagnostics: buffers moved by hpccg_hip_diag_realloc, held until destroy
-    struct Vmm {
-        void* va;  // the mapping (aligned inside the reservation)
-        size_t bytes;
-        hipMemGenericAllocationHandle_t h;
-        void* res;  // the reservation
-        size_t res_bytes;
-    };
-    std::vector<Vmm> vmm;  // diagnostics: hpccg_hip_diag_realloc's VMM mappings (unmapped at destroy)
-    std::vector<double> place_us;  // placement probe: SpMV us per candidate (0 = the creation placement)
-    int place_pick = 0;            // the candidate kept
-    double *d_gen_b = nullptr, *d_gen_x0 = nullptr, *d_gen_xexact = nullptr;
-    long long bytes = 0;       // device bytes held
-    // hipGraph of graph_chunk iterations (kernel arguments are baked in)
-    hipGraphExec_t graph_exec = nullptr;
-    int graph_chunk = 0;
-    int graph_iters = 32;  // 100^3 same-process A/B: 20 442 vs 20 198 it/s at 8 (200^3 +0.15 %); 499 (one graph per solve) 20 033
-    std::vector<CgArgs> graph_args;
-    int graph_kernel = -1;
-    int graph_failed = 0;      // capture refused here (e.g. RCCL inside a graph): eager from then on
-    int graph_used = 0;        // the last solve replayed graphs
-    // hipEvent timing (event_timing option)
-    int event_timing = 0;
-    std::vector<hipEvent_t> ev;
-    double ktimes[4] = {0, 0, 0, 0};
-    std::vector<double> kiter;  // event_timing: per iteration {SpMV ms, update ms}
-    std::vector<double> trace;
-    int last_niters = 0;
-    // hpccg_hip_internal_on_destroy: run at the start of hpccg_hip_matrix_destroy
-    std::vector<std::pair<void (*)(void*), void*>> destroy_hooks;
-};
-
-namespace {
+#pragma GCC visibility push(hidden)
+namespace hpccg::host {
 
 // Canary debug mode (HPCCG_CANARY=1 in the environment when the library first
 // allocates): every matrix buffer gets kCanaryBytes of a NaN
@@ -450,7 +43,7 @@ bool canary_on()
 // contiguous buffers were held and never freed (DESIGN.md 4,
 // tools/diag_carry.py, profiles/r04_carry/). The product library has no path
 // to them at all; the diagnostics variant (-DHPCCG_DIAG_CONTIG) keeps one.
-hipError_t big_malloc(void** p, size_t b, unsigned flags = hipDeviceMallocDefault)
+hipError_t big_malloc(void** p, size_t b, unsigned flags)
 {
     if (!canary_on()) return flags == hipDeviceMallocDefault ? hipMalloc(p, b) : hipExtMallocWithFlags(p, b, flags);
     void* base = nullptr;
@@ -553,16 +146,6 @@ int d2h(hipStream_t s, void* dst, const void* src, size_t bytes)
     return 0;
 }
 
-template <class T>
-int dev_alloc(hpccg_hip_matrix* M, T** p, size_t count, bool zero = false)
-{
-    const size_t b = sizeof(T) * std::max<size_t>(1, count);
-    HIP_TRY(big_malloc(reinterpret_cast<void**>(p), b));
-    if (zero) HIP_TRY(hipMemsetAsync(*p, 0, b, M->stream));  // ordered before M's kernels and copies
-    M->bytes += (long long)b;
-    return 0;
-}
-
 // A marker with a system-scope release on M's stream, waited for: what the
 // kernels left dirty in the L2s is in memory before a buffer is freed (and
 // reused by the next allocation) or read by the host's copy engine. Needed
@@ -589,17 +172,6 @@ int h2d(hpccg_hip_matrix* M, void* dst, const void* src, size_t bytes)
     TRY(flush_stream(M));
     HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, M->stream));
     return flush_stream(M);
-}
-
-template <class T>
-void dev_free(hpccg_hip_matrix* M, T** p, size_t count)
-{
-    if (*p) {
-        (void)flush_stream(M);
-        big_free(*p);
-        M->bytes -= (long long)(sizeof(T) * std::max<size_t>(1, count));
-    }
-    *p = nullptr;
 }
 
 int free_matrix(hpccg_hip_matrix* M)
@@ -673,96 +245,6 @@ int make_streams(hpccg_hip_matrix* M)
 {
     HIP_TRY(hipStreamCreateWithFlags(&M->stream, hipStreamNonBlocking));
     return 0;
-}
-
-// Can the z-slab plan serve rank r? (ghosts from rank+-1 only, contiguous,
-// the planes those ranks own; the condition hpccg_slab_plan enforces)
-bool slab_serves(const int* info, int P, int r)
-{
-    const int* me = info + 4 * r;
-    const int glo = me[1], ghi = me[2];
-    if (glo > 0 && (r == 0 || glo > info[4 * (r - 1)])) return false;
-    if (ghi > 0 && (r == P - 1 || ghi > info[4 * (r + 1)])) return false;
-    if (r > 0 && info[4 * (r - 1) + 3] + info[4 * (r - 1)] != me[3]) return false;
-    return true;
-}
-
-// 1 = slab plan for every rank, 2 = gather plan for every rank (all ranks decide
-// the same from the same all-gathered info).
-int choose_halo_mode(const int* info, int P)
-{
-    if (g_halo_mode == 2) return 2;
-    for (int r = 0; r < P; r++)
-        if (!slab_serves(info, P, r)) return g_halo_mode == 1 ? -1 : 2;
-    return 1;
-}
-
-int owner_of(long long c, const int* info, int P)  // make_local_matrix.cpp:165-173
-{
-    int lo = 0, hi = P - 1;
-    while (lo < hi) {  // last rank whose start_row <= c
-        const int mid = (lo + hi + 1) / 2;
-        if (info[4 * mid + 3] <= c)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
-}
-
-template <class RowLen, class RowAt>
-void gather_externals(int nrow, long long start, const int* info, int P, RowLen row_len, RowAt row_at, GatherPlan& g)
-{
-    std::vector<long long> first;  // externals in order of first appearance
-    std::unordered_map<long long, int> seen;
-    for (int i = 0; i < nrow; i++) {
-        const int len = row_len(i);
-        for (int j = 0; j < len; j++) {
-            long long c;
-            double v;
-            row_at(i, j, &c, &v);
-            if (c >= start && c < start + nrow) continue;
-            if (seen.emplace(c, (int)first.size()).second) first.push_back(c);
-        }
-    }
-    std::vector<std::vector<int>> by_owner(P);
-    std::vector<int> order;
-    for (int i = 0; i < (int)first.size(); i++) {
-        const int q = owner_of(first[i], info, P);
-        if (by_owner[q].empty()) order.push_back(q);
-        by_owner[q].push_back(i);
-    }
-    g.ext_global.assign(first.size(), 0);
-    g.req.assign(P, {});
-    int count = 0;
-    for (int q : order) {
-        g.recv_rank.push_back(q);
-        g.recv_off.push_back(count);
-        g.recv_cnt.push_back((int)by_owner[q].size());
-        for (int i : by_owner[q]) {
-            g.ext_global[count] = first[i];
-            g.ext_of[first[i]] = count;
-            g.req[q].push_back((int)first[i]);
-            count++;
-        }
-    }
-}
-
-// What rank r packs for its requesters, from every rank's requests
-// (reqs_to_me[q] = the global columns rank q needs from r, q's order).
-void gather_sends(long long start, const std::vector<std::vector<int>>& reqs_to_me, GatherPlan& g)
-{
-    g.send_rank.clear();
-    g.send_off.clear();
-    g.send_cnt.clear();
-    g.send_idx.clear();
-    for (int q = 0; q < (int)reqs_to_me.size(); q++) {
-        if (reqs_to_me[q].empty()) continue;
-        g.send_rank.push_back(q);
-        g.send_off.push_back((int)g.send_idx.size());
-        g.send_cnt.push_back((int)reqs_to_me[q].size());
-        for (int c : reqs_to_me[q]) g.send_idx.push_back((int)(c - start));
-    }
 }
 
 // RCCL: requests travel to their owners (the handshake of make_local_matrix
@@ -1575,6 +1057,11 @@ CgArgs make_args(hpccg_hip_matrix* M, const double* b, double* x, int max_iter, 
     return a;
 }
 
+}  // namespace hpccg::host
+#pragma GCC visibility pop
+
+namespace {
+
 // ---------------------------------------------------------------------------
 // exchanges
 // ---------------------------------------------------------------------------
@@ -1698,15 +1185,6 @@ int ensure_events(hpccg_hip_matrix* M, int slots)
 
 // p_k's ring buffer (local rows), as the kernels' cur_p computes it.
 double* ring_p(const CgArgs& a, int k) { return a.p + (size_t)(k % a.nring) * (size_t)a.pstride; }
-
-// The ranks one host thread enqueues: one matrix (a process of an RCCL job, or
-// a single GPU), or every member of an in-process group (hpccg_hip_group_*).
-struct Ranks {
-    hpccg_hip_matrix* const* M;
-    const CgArgs* a;
-    int P;
-    hipEvent_t* ev;  // group: P "ready" events + 1 "reduced" event
-};
 
 int use_device(const Ranks& R, int r)
 {
@@ -2229,6 +1707,11 @@ int clear_state(hpccg_hip_matrix* M)
     return 0;
 }
 
+}  // namespace
+
+#pragma GCC visibility push(hidden)
+namespace hpccg::host {
+
 // A mailbox for the peer all-reduce: uncached device memory where the runtime
 // gives it (every load and store goes to memory: other GPUs write it over
 // xGMI), else fine-grained; every slot empty. A plain (coarse-grained)
@@ -2585,7 +2068,7 @@ int protocol_autotest(hpccg_hip_matrix* M, int* local_ok)
     M->use_graph = ug0;
     M->trace.clear();
     M->last_niters = 0;
-    if (!ok) M->selftest_note += "protocol test: a solve failed (" + g_err + "); ";
+    if (!ok) M->selftest_note += "protocol test: a solve failed (" + last_err() + "); ";
     const bool ran = ok;
     ok = ok && run[0].it == kProtoIters && run[1].it == run[0].it &&
          std::memcmp(&run[0].nr, &run[1].nr, sizeof(double)) == 0 && run[0].trace.size() == run[1].trace.size() &&
@@ -2651,7 +2134,7 @@ int persist_autotest(hpccg_hip_matrix* M, int* local_ok)
         const int rc = solve_ranks(&M, 1, &b, &x, kProtoIters + 1, 0.0, &run[v].it, &run[v].nr, nullptr, 0);
         run[v].resident = M->resident_used;
         if (rc) {
-            if (ok) M->selftest_note += "persistent test: a solve failed (" + g_err + "); ";
+            if (ok) M->selftest_note += "persistent test: a solve failed (" + last_err() + "); ";
             ok = 0;
         }
         run[v].trace = M->trace;
@@ -2713,6 +2196,11 @@ int reset_dot_state(hpccg_hip_matrix* M)
     return 0;
 }
 
+}  // namespace hpccg::host
+#pragma GCC visibility pop
+
+namespace {
+
 // The device error record of every rank (err0: rank 0's, already on the host):
 // a bounded wait that gave up voids the solve (HPCCG_HIP_EHIP). The reference
 // aborts on a failed exchange (exchange_externals.cpp:119-125); this returns.
@@ -2761,6 +2249,11 @@ int check_device_error(hpccg_hip_matrix* const* Ms, int P, const int* err0)
                    rank, (double)Ms[bad_rank]->spin_us, e[0] > 0 && e[0] <= kErrPullWait ? what[e[0]] : "?", e[1],
                    e[0] > 0 && e[0] <= kErrPullWait ? where[e[0]] : "slot", e[2], e[3], e[4] == kPAP ? "p.Ap" : "r.r");
 }
+
+}  // namespace
+
+#pragma GCC visibility push(hidden)
+namespace hpccg::host {
 
 // Solve on the ranks Ms[0..P) (P > 1: an in-process group; P == 1: this
 // process's matrix, exchanging through RCCL when the communicator has peers).
@@ -2942,7 +2435,7 @@ int solve_ranks(hpccg_hip_matrix* const* Ms, int P, const double* const* b_dev, 
                 // captured RCCL or peer copies refused here: eager launches from now on
                 M->graph_failed = 1;
                 std::fprintf(stderr, "hpccg_hip: hipGraph capture unavailable (%s); eager launches\n",
-                             g_err.c_str());
+                             last_err().c_str());
             }
         }
         if (rc == 0) {
@@ -3071,6 +2564,11 @@ int solve_ranks(hpccg_hip_matrix* const* Ms, int P, const double* const* b_dev, 
     }
     return 0;
 }
+
+}  // namespace hpccg::host
+#pragma GCC visibility pop
+
+namespace {
 
 // The resident fused update waits inside its launch for blocks HIP does not
 // promise to run at the same time: with another process holding part of the
@@ -3324,61 +2822,7 @@ int scratch_for(int nparts)
     return 0;
 }
 
-// ---- drop-in cache (hpccg_hip_HPCCG) ----------------------------------------
-// A device matrix per caller HPC_Sparse_Matrix, keyed by its address AND a
-// fingerprint of its contents (sizes, row lengths, every column index and
-// value), so a matrix destroyed and re-created at the same address, or edited
-// in place, is converted again instead of reusing a stale image.
-struct DropinEntry {
-    unsigned long long fp = 0;
-    hpccg_hip_matrix* M = nullptr;
-};
-std::mutex g_dropin_mu;
-std::map<const void*, DropinEntry> g_dropin_cache;
-
-inline unsigned long long mix64(unsigned long long h, unsigned long long v)
-{
-    h ^= v + 0x9e3779b97f4a7c15ULL + (h << 6) + (h >> 2);
-    return h * 0xff51afd7ed558ccdULL;
-}
-
-unsigned long long fingerprint(const HPC_Sparse_Matrix* A)
-{
-    const int n = A->local_nrow;
-    unsigned long long head = mix64(0x1234, (unsigned long long)(unsigned)n);
-    head = mix64(head, (unsigned long long)(unsigned)A->start_row);
-    head = mix64(head, (unsigned long long)(unsigned)A->total_nrow);
-    head = mix64(head, (unsigned long long)(unsigned)A->local_ncol);
-    const int nth = std::max(1, std::min<int>(16, (int)std::thread::hardware_concurrency()));
-    std::vector<unsigned long long> part(nth, 0);
-    auto work = [&](int t) {
-        const int r0 = (int)((long long)n * t / nth), r1 = (int)((long long)n * (t + 1) / nth);
-        unsigned long long h = (unsigned long long)t;
-        for (int i = r0; i < r1; i++) {
-            const int len = A->nnz_in_row[i];
-            h = mix64(h, (unsigned long long)(unsigned)len);
-            const double* v = A->ptr_to_vals_in_row[i];
-            const int* c = A->ptr_to_inds_in_row[i];
-            for (int j = 0; j < len; j++) {
-                unsigned long long bits;
-                std::memcpy(&bits, v + j, 8);
-                h = mix64(h, bits ^ ((unsigned long long)(unsigned)c[j] << 17));
-            }
-        }
-        part[t] = h;
-    };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nth; t++) th.emplace_back(work, t);
-    work(0);
-    for (auto& x : th) x.join();
-    for (int t = 0; t < nth; t++) head = mix64(head, part[t]);
-    return head;
-}
-
-}  // namespace
-
 // ---- in-process rank group -------------------------------------------------
-namespace {
 
 std::atomic<unsigned long long> g_next_group{0};  // ids of the groups made (hpccg_hip_matrix::group_id)
 
@@ -3451,172 +2895,7 @@ int group_make(int nranks, const int* devices, hpccg_hip_matrix** out, Make make
 
 }  // namespace
 
-// ===========================================================================
-// C ABI
-// ===========================================================================
 extern "C" {
-
-int hpccg_hip_abi_version(void) { return 2; }
-
-const char* hpccg_hip_last_error(void) { return g_err.c_str(); }
-
-int hpccg_hip_device_count(int* count)
-{
-    int c = 0;
-    hipError_t e = hipGetDeviceCount(&c);
-    if (e != hipSuccess) c = 0;
-    *count = c;
-    return c > 0 ? 0 : set_err(HPCCG_HIP_ENODEV, "no HIP device");
-}
-
-int hpccg_hip_set_device(int device)
-{
-    HIP_TRY(hipSetDevice(device));
-    return 0;
-}
-
-int hpccg_hip_comm_unique_id(unsigned char id_out[128])
-{
-    ncclUniqueId id;
-    NCCL_TRY(ncclGetUniqueId(&id));
-    static_assert(sizeof(ncclUniqueId) == 128, "ncclUniqueId size");
-    std::memcpy(id_out, &id, 128);
-    return 0;
-}
-
-int hpccg_hip_comm_init(const unsigned char id[128], int nranks, int rank)
-{
-    if (nranks < 1 || rank < 0 || rank >= nranks) return set_err(HPCCG_HIP_EINVAL, "bad nranks/rank");
-    comm_reset();
-    // a 1-rank communicator is created too (bootstrap + RCCL check on one GPU);
-    // the solver still takes its single-rank path when nranks == 1
-    ncclUniqueId uid;
-    std::memcpy(&uid, id, 128);
-    NCCL_TRY(ncclCommInitRank(&g_comm.comm, nranks, uid, rank));
-    g_comm.nranks = nranks;
-    g_comm.rank = rank;
-    return 0;
-}
-
-int hpccg_hip_comm_init_host(int nranks, int rank, hpccg_hip_allgather_fn allgather, void* ctx)
-{
-    if (nranks < 1 || rank < 0 || rank >= nranks || !allgather)
-        return set_err(HPCCG_HIP_EINVAL, "bad nranks/rank or no all-gather callback");
-    comm_reset();
-    g_comm.nranks = nranks;
-    g_comm.rank = rank;
-    g_comm.ag = allgather;
-    g_comm.ag_ctx = ctx;
-    // the callback is collective: every rank must see every rank in order
-    std::vector<int> all(nranks, -1);
-    int rc = comm_allgather(&rank, all.data(), sizeof rank);
-    for (int q = 0; q < nranks && rc == 0; q++)
-        if (all[q] != q) rc = set_err(HPCCG_HIP_EINVAL, "host all-gather: slot %d holds rank %d", q, all[q]);
-    if (rc) comm_reset();
-    return rc;
-}
-
-int hpccg_hip_comm_destroy(void)
-{
-    comm_reset();
-    return 0;
-}
-
-int hpccg_hip_comm_mode(int* mode)
-{
-    if (!mode) return set_err(HPCCG_HIP_EINVAL, "mode is NULL");
-    *mode = g_comm.comm ? 1 : (g_comm.ag ? 2 : 0);
-    return 0;
-}
-
-int hpccg_hip_comm_size(int* nranks, int* rank)
-{
-    if (nranks) *nranks = g_comm.nranks;
-    if (rank) *rank = g_comm.rank;
-    return 0;
-}
-
-int hpccg_hip_comm_allreduce_host(double* vals, int n, int op)
-{
-    if (!vals || n < 0 || op < 0 || op > 2) return set_err(HPCCG_HIP_EINVAL, "bad argument");
-    if (comm_host() && n > 0) {  // every rank's values, reduced in rank order
-        std::vector<double> all((size_t)n * g_comm.nranks);
-        TRY(comm_allgather(vals, all.data(), sizeof(double) * n));
-        for (int i = 0; i < n; i++) {
-            double v = op == 0 ? 0.0 : all[i];
-            for (int q = 0; q < g_comm.nranks; q++) {
-                const double w = all[(size_t)q * n + i];
-                v = op == 0 ? v + w : op == 1 ? std::min(v, w) : std::max(v, w);
-            }
-            vals[i] = v;
-        }
-        return 0;
-    }
-    if (!g_comm.comm || n == 0) return 0;
-    double* d = nullptr;
-    hipStream_t s = nullptr;
-    HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    HIP_TRY(hipMalloc(&d, sizeof(double) * n));
-    TRY(h2d_stream(s, d, vals, sizeof(double) * n));
-    const ncclRedOp_t ops[3] = {ncclSum, ncclMin, ncclMax};
-    NCCL_TRY(ncclAllReduce(d, d, n, ncclFloat64, ops[op], g_comm.comm, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipMemcpy(vals, d, sizeof(double) * n, hipMemcpyDeviceToHost));
-    (void)hipFree(d);
-    (void)hipStreamDestroy(s);
-    return 0;
-}
-
-int hpccg_hip_transport_verdict(const int local[3], int verdict[3])
-{
-    if (!local || !verdict) return set_err(HPCCG_HIP_EINVAL, "NULL argument");
-    if (!comm_up()) return set_err(HPCCG_HIP_EINVAL, "no communicator (hpccg_hip_comm_init / _init_host first)");
-    return transport_verdict(local, verdict);
-}
-
-int hpccg_hip_runtime_info(int ints_out[6], char* pci_bus_id, int pci_cap, char* rccl_path, char* hip_path,
-                           int path_cap)
-{
-    if (!ints_out) return set_err(HPCCG_HIP_EINVAL, "ints_out is NULL");
-    int dev = 0, v = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    ints_out[0] = ints_out[1] = 0;
-    if (g_comm.comm) {
-        NCCL_TRY(ncclCommCount(g_comm.comm, &ints_out[0]));
-        NCCL_TRY(ncclCommUserRank(g_comm.comm, &ints_out[1]));
-    }
-    NCCL_TRY(ncclGetVersion(&v));
-    ints_out[2] = v;
-    HIP_TRY(hipRuntimeGetVersion(&v));
-    ints_out[3] = v;
-    HIP_TRY(hipDriverGetVersion(&v));
-    ints_out[4] = v;
-    ints_out[5] = dev;
-    if (pci_bus_id && pci_cap > 0) HIP_TRY(hipDeviceGetPCIBusId(pci_bus_id, pci_cap, dev));
-    // the files the RCCL and HIP entry points of this library resolved to
-    auto where = [](const void* sym, char* out, int cap) {
-        Dl_info di;
-        if (!out || cap <= 0) return;
-        if (dladdr(sym, &di) && di.dli_fname)
-            std::snprintf(out, cap, "%s", di.dli_fname);
-        else
-            std::snprintf(out, cap, "?");
-    };
-    where(reinterpret_cast<const void*>(&ncclGetVersion), rccl_path, path_cap);
-    where(reinterpret_cast<const void*>(&hipRuntimeGetVersion), hip_path, path_cap);
-    return 0;
-}
-
-int hpccg_hip_device_name(char* buf, int cap, int* cus)
-{
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, dev));
-    if (buf && cap > 0) std::snprintf(buf, cap, "%s (%s)", prop.name[0] ? prop.name : "AMD Instinct GPU", prop.gcnArchName);
-    if (cus) *cus = prop.multiProcessorCount;
-    return 0;
-}
 
 int hpccg_hip_matrix_create(const HPC_Sparse_Matrix* A, hpccg_hip_matrix** out)
 {
@@ -3823,26 +3102,6 @@ int hpccg_hip_group_solve(hpccg_hip_matrix* const* Ms, int nranks, const double*
     return rc;
 }
 
-int hpccg_hip_set_halo_mode(int mode)
-{
-    if (mode < 0 || mode > 2) return set_err(HPCCG_HIP_EINVAL, "halo mode must be 0, 1 or 2");
-    g_halo_mode = mode;
-    return 0;
-}
-
-int hpccg_hip_set_keep_sell(int keep)
-{
-    g_keep_sell = keep ? 1 : 0;
-    return 0;
-}
-
-int hpccg_hip_set_placement_probe(int tries)
-{
-    if (tries < -1 || tries > 16) return set_err(HPCCG_HIP_EINVAL, "placement probe: -1 (auto), 0 (off) or 1..16");
-    g_place_tries = tries;
-    return 0;
-}
-
 int hpccg_hip_matrix_destroy(hpccg_hip_matrix* M) { return free_matrix(M); }
 
 // ---------------------------------------------------------------------------
@@ -3892,8 +3151,6 @@ int hpccg_hip_internal_on_destroy(hpccg_hip_matrix* M, void (*fn)(void*), void* 
     return 0;
 }
 
-int hpccg_hip_internal_set_error(int code, const char* msg) { return set_err(code, "%s", msg ? msg : ""); }
-
 int hpccg_hip_matrix_info(const hpccg_hip_matrix* M, long long info[8])
 {
     if (!M || !info) return set_err(HPCCG_HIP_EINVAL, "NULL argument");
@@ -3914,165 +3171,6 @@ int hpccg_hip_matrix_vectors(hpccg_hip_matrix* M, double** b, double** x0, doubl
     if (b) *b = M->d_gen_b;
     if (x0) *x0 = M->d_gen_x0;
     if (xexact) *xexact = M->d_gen_xexact;
-    return 0;
-}
-
-// Options (hpccg_hip.h documents each): twelve settings of the solve --
-// use_graph, spmv_kernel, fuse_p, fold, x_defer, x_ring, fuse_update,
-// resident_update, graph_chunk, a2_ring, peer_allreduce, halo_pull -- and
-// diagnostics (event_timing, force_comm, spin_budget_us, nt, dbg_*). Variants
-// that measured even or slower than the defaults were removed (DESIGN.md 4,
-// "What was dropped"); git history keeps them.
-int hpccg_hip_set_option(hpccg_hip_matrix* M, const char* key, long long value)
-{
-    if (!M || !key) return set_err(HPCCG_HIP_EINVAL, "NULL argument");
-    if (!std::strcmp(key, "use_graph")) {
-        M->use_graph = (int)value;
-    } else if (!std::strcmp(key, "event_timing")) {
-        M->event_timing = (int)value;
-    } else if (!std::strcmp(key, "fuse_p")) {
-        M->fuse_p = value < 0 ? -1 : (value ? 1 : 0);
-    } else if (!std::strcmp(key, "x_defer")) {
-        if (value < 0 || value > 2)
-            return set_err(HPCCG_HIP_EINVAL, "x_defer must be 0 (every iteration), 1 (batched in the update) or 2 "
-                                             "(beside the SpMV)");
-        M->x_defer = (int)value;
-    } else if (!std::strcmp(key, "x_ring")) {
-        if (value != -1 && (value < 2 || value > kXRingMax))
-            return set_err(HPCCG_HIP_EINVAL, "x_ring must be -1 (auto) or 2..%d", kXRingMax);
-        const int prev = M->x_ring;
-        M->x_ring = (int)value;
-        if (x_ring_effective(M) > M->ring_alloc) {
-            HIP_TRY(hipSetDevice(M->device));
-            HIP_TRY(hipStreamSynchronize(M->stream));
-            const int rc = alloc_ring(M, x_ring_effective(M));
-            if (rc) {
-                M->x_ring = prev;
-                return rc;
-            }
-        }
-    } else if (!std::strcmp(key, "fuse_update")) {
-        M->fuse_update = value < 0 ? -1 : (value > 2 ? 2 : (int)value);
-    } else if (!std::strcmp(key, "resident_update")) {
-        if (value < -1 || value > 1)
-            return set_err(HPCCG_HIP_EINVAL, "resident_update: -1 (auto: the persistent launch where it fits), 0 off "
-                                             "or 1 (the per-iteration resident launch only)");
-        M->resident_update = (int)value;
-        if (value) M->resident_failed = 0;
-    } else if (!std::strcmp(key, "nt")) {
-        if (value < -1 || value > 1)
-            return set_err(HPCCG_HIP_EINVAL, "nt must be -1 (auto: images beyond the Infinity Cache), 0 or 1");
-        M->nt_opt = (int)value;  // (the graph cache compares the kernel arguments: a changed a.nt re-captures)
-    } else if (!std::strcmp(key, "graph_chunk")) {
-        if (value < 1 || value > 4096) return set_err(HPCCG_HIP_EINVAL, "graph_chunk must be 1..4096");
-        M->graph_iters = (int)value;
-    } else if (!std::strcmp(key, "fold")) {
-        if (value < -1 || value > 1)
-            return set_err(HPCCG_HIP_EINVAL, "fold must be -1 (auto: both dots in their producers), 1 or 0 (k_finalize)");
-        M->fold = (int)value;
-    } else if (!std::strcmp(key, "a2_ring")) {
-        if (value != -1 && value != 0 && value != kA2RingDefault)
-            return set_err(HPCCG_HIP_EINVAL, "a2_ring must be -1 (auto: %d), 0 (register loads) or %d", kA2RingDefault,
-                           kA2RingDefault);
-        M->a2_ring = value < 0 ? kA2RingDefault : (int)value;
-    } else if (!std::strcmp(key, "force_comm")) {
-        if (value < 0 || value > 2) return set_err(HPCCG_HIP_EINVAL, "force_comm is 0, 1 or 2");
-        M->force_comm = (int)value;
-    } else if (!std::strcmp(key, "spin_budget_us")) {
-        if (value < 1 || value > 20000000LL) return set_err(HPCCG_HIP_EINVAL, "spin_budget_us must be 1..2e7");
-        M->spin_us = value;
-    } else if (!std::strcmp(key, "peer_allreduce")) {
-        M->peer_ar = value < 0 ? -1 : (value ? 1 : 0);
-    } else if (!std::strcmp(key, "halo_pull")) {
-        // -1 auto, 0 off (the RCCL / peer-copy planes), 1 k_pull where possible, 2 in-launch where the
-        // peer all-reduce runs (else 1); 3 (diagnostics, the 1-rank emulation): in-launch with no rows
-        M->halo_pull = value < 0 ? -1 : (value > 3 ? 3 : (int)value);
-    } else if (!std::strcmp(key, "dbg_timeline")) {
-        if (value != 0 && value != 1) return set_err(HPCCG_HIP_EINVAL, "dbg_timeline must be 0 or 1");
-        HIP_TRY(hipSetDevice(M->device));
-        if (M->d_tl) {
-            dev_free(M, &M->d_tl, (size_t)M->tl_units * kTlWords);
-            M->tl_units = 0;
-        }
-        if (value) {
-            M->tl_units = 3 * M->nslices + 1024;  // >= the blocks of any SpMV launch (units, side, ghost, update)
-            TRY(dev_alloc(M, &M->d_tl, (size_t)M->tl_units * kTlWords, true));
-        }  // the graph cache compares the kernel arguments: a changed dbg_tl re-captures
-    } else if (!std::strcmp(key, "dbg_resident_stall")) {
-        M->dbg_resident_stall = value ? 1 : 0;
-    } else if (!std::strcmp(key, "dbg_withhold")) {
-        if (value < 0 || value > M->nslices) return set_err(HPCCG_HIP_EINVAL, "dbg_withhold must be 0..nslices");
-        M->dbg_withhold = (int)value;
-    } else if (!std::strcmp(key, "spmv_kernel")) {
-        if (value != -1 && !spmv_kernel_ok((int)value))
-            return set_err(HPCCG_HIP_EINVAL, "spmv_kernel must be -1 (auto), 0 (SELL-512), 1 (SELL-512-A direct) or "
-                                             "2 (SELL-512-A pair windows)");
-        if (value >= 0 && !kernel_available(M, (int)value))
-            return set_err(HPCCG_HIP_EINVAL, "spmv_kernel %lld: its image was not built for this matrix%s", value,
-                           value == kSpmvSell ? " (hpccg_hip_set_keep_sell(1) before creation keeps SELL-512)" : "");
-        M->kernel_opt = (int)value;
-        M->kernel = choose_kernel(M);
-    } else {
-        return set_err(HPCCG_HIP_EINVAL, "unknown option '%s'", key);
-    }
-    return 0;
-}
-
-int hpccg_hip_get_option(const hpccg_hip_matrix* M, const char* key, long long* value)
-{
-    if (!M || !key || !value) return set_err(HPCCG_HIP_EINVAL, "NULL argument");
-    if (!std::strcmp(key, "use_graph")) *value = M->use_graph;
-    else if (!std::strcmp(key, "spmv_kernel")) *value = M->kernel;
-    else if (!std::strcmp(key, "event_timing")) *value = M->event_timing;
-    else if (!std::strcmp(key, "fuse_p")) *value = fuse_p_effective(M) ? 1 : 0;
-    else if (!std::strcmp(key, "fold")) *value = fold_effective(M);
-    else if (!std::strcmp(key, "x_defer")) *value = x_defer_effective(M);
-    else if (!std::strcmp(key, "x_ring")) *value = x_ring_effective(M);
-    else if (!std::strcmp(key, "fuse_update")) *value = fuse_update_effective(M) ? 1 : 0;
-    else if (!std::strcmp(key, "resident_update"))
-        *value = persist_ok(M) ? kResidentAuto : resident_of(M) ? 1 : 0;
-    else if (!std::strcmp(key, "resident_retries")) *value = M->resident_retries;
-    else if (!std::strcmp(key, "halo_mode")) *value = M->nranks == 1 ? 0 : (M->general ? 2 : 1);
-    else if (!std::strcmp(key, "graph_chunk")) {  // effective: see graph_chunk_of
-        long long c = std::max(1, M->graph_iters);
-        if (fuse_update_effective(M)) c += c & 1;
-        if (multi_of(M) && !rhalo_of(M)) {
-            const long long ring = x_defer_effective(M) ? x_ring_effective(M) : (fuse_p_effective(M) ? 2 : 1);
-            c = (c + ring - 1) / ring * ring;
-        }
-        *value = c;
-    }
-    else if (!std::strcmp(key, "graph_used")) *value = M->graph_used;
-    else if (!std::strcmp(key, "force_comm")) *value = M->force_comm;
-    else if (!std::strcmp(key, "spin_budget_us")) *value = M->spin_us;
-    else if (!std::strcmp(key, "dbg_withhold")) *value = M->dbg_withhold;
-    else if (!std::strcmp(key, "dbg_timeline")) *value = M->d_tl ? 1 : 0;
-    else if (!std::strcmp(key, "peer_allreduce")) *value = peer_ar_of(M) ? 1 : 0;
-    else if (!std::strcmp(key, "group_fold")) *value = M->gfold_used;
-    else if (!std::strcmp(key, "rhalo")) *value = rhalo_of(M) ? 1 : 0;
-    else if (!std::strcmp(key, "halo_pull")) {
-        CgArgs a{};
-        a.peer_ar = peer_ar_of(M) ? 1 : 0;
-        a.fold = fold_effective(M);
-        *value = pull_of(M) ? (pull_in_of(M, a) ? 2 : 1) : 0;
-    }
-    else if (!std::strcmp(key, "a2_ring")) *value = a2_ring_effective(M);
-    else if (!std::strcmp(key, "nt_store")) *value = nt_store_effective(M) ? 1 : 0;
-    else if (!std::strcmp(key, "num_external")) *value = M->general ? M->ghost_hi : M->ghost_lo + M->ghost_hi;
-    else if (!std::strcmp(key, "has_sell")) *value = M->has_sell;
-    else if (!std::strcmp(key, "has_a")) *value = M->has_a;
-    else if (!std::strcmp(key, "a_reject")) *value = M->a_reject;
-    else if (!std::strcmp(key, "has_pairs")) *value = M->has_pairs;
-    else if (!std::strcmp(key, "a_width")) *value = M->a_width;
-    else if (!std::strcmp(key, "lds_doubles")) *value = M->has_pairs ? M->alds2_doubles : 0;
-    else if (!std::strcmp(key, "nt")) *value = nt_load_of(M) ? 1 : 0;
-    else if (!std::strcmp(key, "device_bytes")) *value = M->bytes;
-    else if (!std::strcmp(key, "placement_pick")) *value = M->place_pick;
-    else if (!std::strcmp(key, "peer_auto_ok")) *value = M->peer_auto_ok;
-    else if (!std::strcmp(key, "pull_auto_ok")) *value = M->pull_auto_ok;
-    else if (!std::strcmp(key, "proto_auto_ok")) *value = M->proto_auto_ok;
-    else if (!std::strcmp(key, "persist_auto_ok")) *value = M->persist_auto_ok;
-    else return set_err(HPCCG_HIP_EINVAL, "unknown option '%s'", key);
     return 0;
 }
 
@@ -4101,8 +3199,6 @@ int hpccg_hip_solve_device(hpccg_hip_matrix* M, const double* b_dev, double* x_d
     HIP_TRY(hipMemcpyAsync(x_dev, x, sizeof(double) * M->nrow, hipMemcpyDeviceToDevice, M->stream));
     return wait_matrix(M);
 }
-
-namespace {
 
 // The caller's b and x into d_b / d_x: pageable copies straight from the
 // caller's memory (the runtime moves them at ~56 GB/s on the box; a pinned
@@ -4141,325 +3237,12 @@ int solve_host(hpccg_hip_matrix* M, const double* b, const double* x, int max_it
     return 0;
 }
 
-}  // namespace
-
 int hpccg_hip_solve(hpccg_hip_matrix* M, const double* b, double* x, int max_iter, double tolerance, int* niters,
                     double* normr, double* times, int print)
 {
     if (!M || !b || !x || !niters || !normr) return set_err(HPCCG_HIP_EINVAL, "NULL argument");
     TRY(solve_host(M, b, x, max_iter, tolerance, niters, normr, times, print));
     return download_x(M, x);
-}
-
-int hpccg_hip_diag_spmv(hpccg_hip_matrix* M, int kernel, int reps, double* avg_us)
-{
-    if (!M || !avg_us || reps < 1) return set_err(HPCCG_HIP_EINVAL, "bad argument");
-    const bool stream = kernel == kDiagStreamA && M->has_a;
-    if (!stream && (!spmv_kernel_ok(kernel) || !kernel_available(M, kernel)))
-        return set_err(HPCCG_HIP_EINVAL, "spmv_kernel %d is not available for this matrix", kernel);
-    HIP_TRY(hipSetDevice(M->device));
-    TRY(ensure_hist(M, 2));
-    const int keep = M->kernel;
-    if (!stream) M->kernel = kernel;  // make_args sizes the grid for that kernel
-    CgArgs a = make_args(M, M->d_b, M->d_x, 2, 0.0);
-    M->kernel = keep;
-    auto launch = [&]() {
-        if (stream)
-            launch_stream_a(a, M->stream);
-        else
-            launch_cg_spmv(a, kernel, true, M->stream);
-    };
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    launch();  // warm
-    HIP_TRY(hipEventRecord(e0, M->stream));
-    for (int i = 0; i < reps; i++) launch();
-    HIP_TRY(hipEventRecord(e1, M->stream));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    *avg_us = 1e3 * ms / reps;
-    return 0;
-}
-
-// Physical placement probe: the CG iteration rate of a large
-// image depends on where in HBM its values and the p ring were placed (306-350
-// us per 200^3 SpMV on one box, same code, same virtual layout). Time a few
-// CG iterations on the creation placement and on `tries` candidate
-// allocations (each allocated while the earlier ones are held, so each lands
-// elsewhere), keep the fastest, free the rest. Values are copied, the ring is
-// zeroed as alloc_ring leaves it; nothing else moves and no result changes.
-// Off unless asked for (hpccg_hip_set_placement_probe / bench.py --placement).
-// Round 3's contiguous candidates found the fast placements and corrupted
-// other buffers (big_malloc); plain candidates are safe and rarely faster.
-constexpr int kPlaceIters = 10;  // CG iterations per candidate (eager, event-timed)
-
-// Median SpMV + update time (us) of iterations 2.. of a short eager solve on
-// scratch b, x. A rank of an RCCL job or a group member is timed as one rank
-// (no halo, no all-reduce: the probe must not make collective calls that the
-// other ranks' probes might not match; the ghost rows it leaves unwritten are
-// the ring's zeros).
-int probe_time(hpccg_hip_matrix* M, const double* b, double* x, double* us)
-{
-    const int nr = M->nranks, ev = M->event_timing, gr = M->use_graph;
-    M->nranks = 1;
-    M->event_timing = 1;
-    M->use_graph = 0;
-    int it = 0;
-    double normr = 0.0;
-    int rc = 0;
-    if (hipMemsetAsync(x, 0, sizeof(double) * M->npad, M->stream) != hipSuccess)
-        rc = set_err(HPCCG_HIP_EHIP, "placement probe: hipMemsetAsync failed");
-    if (!rc) rc = solve_ranks(&M, 1, &b, &x, kPlaceIters, 0.0, &it, &normr, nullptr, 0);
-    M->nranks = nr;
-    M->event_timing = ev;
-    M->use_graph = gr;
-    if (rc) return rc;
-    std::vector<double> v;
-    for (int i = 2; i <= it; i++) v.push_back(M->kiter[2 * i] + M->kiter[2 * i + 1]);
-    if (v.empty()) return set_err(HPCCG_HIP_EINVAL, "placement probe: the solve ran %d iterations", it);
-    std::nth_element(v.begin(), v.begin() + v.size() / 2, v.end());
-    *us = 1e3 * v[v.size() / 2];
-    return 0;
-}
-
-// The probe's candidates are plain allocations (big_malloc's reason). Only
-// the diagnostics variant of the library (-DHPCCG_DIAG_CONTIG,
-// tools/build_variant.sh) lets tools/diag_carry.py ask for others:
-// HPCCG_PROBE_ALLOC = hipExtMallocWithFlags flags (4: contiguous -- this
-// corrupted other buffers). HPCCG_PROBE_KEEP=1 holds the dropped candidates
-// for the life of the process instead of freeing them.
-static unsigned probe_alloc_flags()
-{
-#ifdef HPCCG_DIAG_CONTIG
-    const char* e = std::getenv("HPCCG_PROBE_ALLOC");
-    return e && *e ? (unsigned)std::atoi(e) : hipDeviceMallocDefault;
-#else
-    return hipDeviceMallocDefault;
-#endif
-}
-static bool probe_keep()
-{
-    const char* e = std::getenv("HPCCG_PROBE_KEEP");
-    return e && e[0] == '1';
-}
-static std::vector<double*> g_probe_held;
-
-int hpccg_hip_probe_placement(hpccg_hip_matrix* M, int tries)
-{
-    if (!M) return set_err(HPCCG_HIP_EINVAL, "NULL argument");
-    if (tries < 0 || tries > 16) return set_err(HPCCG_HIP_EINVAL, "tries must be 0..16");
-    M->place_us.clear();
-    M->place_pick = 0;
-    if (!tries || !M->has_a || !M->d_aval || !M->d_pbuf) return 0;
-    HIP_TRY(hipSetDevice(M->device));
-    HIP_TRY(hipStreamSynchronize(M->stream));
-    // b | x of the timed solves, each padded to npad rows like the solver's
-    // own vectors (the slice kernels load whole slices)
-    const size_t n = M->npad;
-    double* scratch = nullptr;
-    HIP_TRY(hipMalloc(&scratch, 2 * sizeof(double) * n));
-    auto done = [&](int rc) {
-        (void)flush_stream(M);  // the timed solves ran with the timing events (no system-scope release)
-        (void)hipFree(scratch);
-        (void)hipGetLastError();  // a refused candidate allocation only ends a phase
-        M->trace.clear();         // the probe's solves are not the caller's
-        M->last_niters = 0;
-        M->kiter.clear();
-        for (double& t : M->ktimes) t = 0.0;
-        return rc;
-    };
-    // b: every 32-bit word 0x3ff00000 (each double ~1.0000002; only the rate matters)
-    if (hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(scratch), 0x3ff00000u, 2 * n, M->stream) != hipSuccess)
-        return done(set_err(HPCCG_HIP_EHIP, "placement probe: hipMemsetD32Async failed"));
-    double us = 0.0;
-    int rc = probe_time(M, scratch, scratch + n, &us);
-    if (rc) return done(rc);
-    M->place_us.push_back(us);
-    double best_us = us;
-    // phase 0 places the values (copied), 1 the p ring, 2 r, 3 Ap (zeroed, as
-    // workspace allocation leaves them), each against the others' kept placement
-    const ptrdiff_t poff = M->d_p - M->d_pbuf, roff = M->d_r - M->d_rbuf;
-    for (int phase = 0; phase < kPlacePhases; phase++) {
-        if (phase == 2 && M->pull_auto_ok) continue;  // the neighbours have this r mapped (halo_pull)
-        double** const slots[kPlacePhases] = {&M->d_aval, &M->d_pbuf, &M->d_rbuf, &M->d_Ap};
-        const size_t counts[kPlacePhases] = {(size_t)std::max<long long>(1, M->a_slots),
-                                             (size_t)M->pstride * M->ring_alloc, (size_t)M->pstride, M->npad};
-        double** slot = slots[phase];
-        const size_t bytes = sizeof(double) * counts[phase];
-        auto set = [&](double* q) {
-            *slot = q;
-            if (phase == 1) M->d_p = q + poff;
-            if (phase == 2) M->d_r = q + roff;
-        };
-        std::vector<double*> cand{*slot};
-        size_t best = 0;
-        for (int t = 0; t < tries && !rc; t++) {
-            size_t fr = 0, tot = 0;
-            if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < bytes + (size_t(8) << 30)) break;  // headroom
-            double* q = nullptr;
-            if (big_malloc(reinterpret_cast<void**>(&q), bytes, probe_alloc_flags()) != hipSuccess)
-                break;
-            cand.push_back(q);
-            const hipError_t e = phase == 0 ? hipMemcpyAsync(q, cand[0], bytes, hipMemcpyDeviceToDevice, M->stream)
-                                            : hipMemsetAsync(q, 0, bytes, M->stream);
-            if (e != hipSuccess) {
-                rc = set_err(HPCCG_HIP_EHIP, "placement probe: filling candidate %d failed", t + 1);
-                break;
-            }
-            set(q);
-            rc = probe_time(M, scratch, scratch + n, &us);
-            if (rc) break;
-            M->place_us.push_back(us);
-            if (us < best_us) {
-                best_us = us;
-                best = cand.size() - 1;
-            }
-        }
-        if (rc) best = 0;
-        (void)flush_stream(M);  // no launch reads the others any more, and nothing of theirs is left in cache
-        set(cand[best]);
-        for (size_t i = 0; i < cand.size(); i++)
-            if (i != best) {
-                if (probe_keep())
-                    g_probe_held.push_back(cand[i]);  // diagnostics: never handed out again
-                else
-                    big_free(cand[i]);
-            }
-        if (phase > 0 && hipMemsetAsync(cand[best], 0, bytes, M->stream) != hipSuccess && !rc)
-            rc = set_err(HPCCG_HIP_EHIP, "placement probe: hipMemsetAsync failed");  // the solves' values
-        M->place_pick |= (int)best << (8 * phase);
-        if (rc) break;
-    }
-    return done(rc);
-}
-
-int hpccg_hip_diag_placement(const hpccg_hip_matrix* M, double* us_out, int cap)
-{
-    if (!M || (!us_out && cap > 0)) return set_err(HPCCG_HIP_EINVAL, "NULL argument");
-    const int n = (int)M->place_us.size();
-    for (int i = 0; i < std::min(n, cap); i++) us_out[i] = M->place_us[i];
-    return n;
-}
-
-// Diagnostics: a mapping through the VMM API at a chosen virtual alignment.
-int vmm_alloc(hpccg_hip_matrix* M, size_t bytes, size_t align, double** out)
-{
-    hipMemAllocationProp prop = {};
-    prop.type = hipMemAllocationTypePinned;
-    prop.location.type = hipMemLocationTypeDevice;
-    prop.location.id = M->device;
-    size_t gran = 0;
-    HIP_TRY(hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityRecommended));
-    const size_t sz = (bytes + gran - 1) / gran * gran;
-    // reserve align more and map at an aligned address inside (the
-    // reservation's own alignment argument is not honoured above 2 MB here)
-    align = std::max(align, gran);
-    void* res = nullptr;
-    HIP_TRY(hipMemAddressReserve(&res, sz + align, gran, nullptr, 0));
-    const uintptr_t a0 = (reinterpret_cast<uintptr_t>(res) + align - 1) / align * align;
-    void* va = reinterpret_cast<void*>(a0);
-    hipMemGenericAllocationHandle_t h;
-    HIP_TRY(hipMemCreate(&h, sz, &prop, 0));
-    HIP_TRY(hipMemMap(va, sz, 0, h, 0));
-    hipMemAccessDesc ad = {};
-    ad.location = prop.location;
-    ad.flags = hipMemAccessFlagsProtReadWrite;
-    HIP_TRY(hipMemSetAccess(va, sz, &ad, 1));
-    M->vmm.push_back({va, sz, h, res, sz + align});
-    *out = static_cast<double*>(va);
-    return 0;
-}
-
-int hpccg_hip_diag_realloc(hpccg_hip_matrix* M, int which, unsigned long long* va_out)
-{
-    if (!M) return set_err(HPCCG_HIP_EINVAL, "NULL argument");
-    const int mode = which >> 8;
-    which &= 255;
-    HIP_TRY(hipSetDevice(M->device));
-    HIP_TRY(hipStreamSynchronize(M->stream));
-    double** buf;
-    size_t n;
-    switch (which) {
-    case 0: buf = &M->d_aval; n = (size_t)std::max<long long>(1, M->a_slots); break;
-    case 1: buf = &M->d_pbuf; n = (size_t)M->pstride * M->ring_alloc; break;
-    case 2: buf = &M->d_rbuf; n = (size_t)M->pstride; break;
-    case 3: buf = &M->d_Ap; n = M->npad; break;
-    case 4: buf = &M->d_x; n = M->npad; break;
-    default: return set_err(HPCCG_HIP_EINVAL, "which must be 0..4");
-    }
-    if (mode < 0 || mode > 6) return set_err(HPCCG_HIP_EINVAL, "mode must be 0..6");
-#ifndef HPCCG_DIAG_CONTIG
-    if (mode == 1)
-        return set_err(HPCCG_HIP_EINVAL, "mode 1 (physically contiguous memory) exists only in the diagnostics "
-                                         "variant of the library (-DHPCCG_DIAG_CONTIG): it corrupted other buffers");
-#endif
-    if (!*buf) return set_err(HPCCG_HIP_EINVAL, "buffer %d not allocated", which);
-    // the neighbours pull from this r through their IPC mappings of it (halo_pull):
-    // a moved r would leave them reading the old buffer
-    if (which == 2 && M->pull_auto_ok)
-        return set_err(HPCCG_HIP_EINVAL, "r cannot move: the neighbours have it mapped (halo_pull)");
-    double* nb = nullptr;
-    const size_t bytes = sizeof(double) * n;
-    if (mode == 0) {
-        HIP_TRY(big_malloc(reinterpret_cast<void**>(&nb), bytes));
-#ifdef HPCCG_DIAG_CONTIG
-    } else if (mode == 1) {
-        HIP_TRY(big_malloc(reinterpret_cast<void**>(&nb), bytes, hipDeviceMallocContiguous));
-#endif
-    } else if (mode == 5) {  // fine-grained (coherent) device memory
-        HIP_TRY(big_malloc(reinterpret_cast<void**>(&nb), bytes, hipDeviceMallocFinegrained));
-    } else if (mode == 6) {
-        HIP_TRY(big_malloc(reinterpret_cast<void**>(&nb), bytes, hipDeviceMallocUncached));
-    } else {  // VMM at 2 MB, 64 MB or 1 GB virtual alignment
-        const size_t align = mode == 2 ? (size_t(1) << 21) : mode == 3 ? (size_t(1) << 26) : (size_t(1) << 30);
-        TRY(vmm_alloc(M, bytes, align, &nb));
-    }
-    HIP_TRY(hipMemcpyAsync(nb, *buf, bytes, hipMemcpyDeviceToDevice, M->stream));
-    HIP_TRY(hipStreamSynchronize(M->stream));
-    bool mapped = false;  // a VMM mapping is released at destroy, not hipFree'd
-    for (const auto& v : M->vmm) mapped = mapped || v.va == *buf;
-    if (!mapped) M->graveyard.push_back(*buf);  // held: the new buffer gets other physical memory
-    const ptrdiff_t poff = M->d_p - M->d_pbuf, roff = M->d_r - M->d_rbuf;
-    *buf = nb;
-    if (which == 1) M->d_p = M->d_pbuf + poff;
-    if (which == 2) M->d_r = M->d_rbuf + roff;
-    if (va_out) *va_out = reinterpret_cast<unsigned long long>(nb);
-    return 0;  // the graph cache compares kernel arguments: the next solve re-captures
-}
-
-int hpccg_hip_diag_canary_check(int* enabled, char* report, int cap)
-{
-    if (enabled) *enabled = canary_on() ? 1 : 0;
-    std::string rep;
-    const int bad = canary_check(&rep);
-    if (report && cap > 0) std::snprintf(report, (size_t)cap, "%s", rep.c_str());
-    return bad;
-}
-
-int hpccg_hip_diag_timeline(const hpccg_hip_matrix* M, unsigned long long* out, int cap)
-{
-    if (!M || !out) return set_err(HPCCG_HIP_EINVAL, "NULL argument");
-    if (!M->d_tl) return set_err(HPCCG_HIP_EINVAL, "dbg_timeline is off");
-    const int n = std::min(cap, M->tl_units);
-    HIP_TRY(hipSetDevice(M->device));
-    HIP_TRY(hipStreamSynchronize(M->stream));
-    HIP_TRY(hipMemcpy(out, M->d_tl, (size_t)n * kTlWords * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return n;
-}
-
-int hpccg_hip_diag_slot_plan(int units, int grid, int spu, int rev, int* last_unit, int cap, int* top_group)
-{
-    if (!last_unit || !top_group || units < 1) return set_err(HPCCG_HIP_EINVAL, "bad argument");
-    const int ng = (units * spu + 63) / 64;
-    if (ng > cap) return set_err(HPCCG_HIP_EINVAL, "cap %d < %d groups", cap, ng);
-    const int r = slot_plan(units, grid, spu, rev, last_unit, top_group);
-    if (r < 0) return set_err(HPCCG_HIP_EINVAL, "bad launch shape");
-    return r;
 }
 
 int hpccg_hip_kernel_times(const hpccg_hip_matrix* M, double out[4])
@@ -4548,171 +3331,6 @@ int hpccg_hip_waxpby(int n, double alpha, const double* x_dev, double beta, cons
     launch_waxpby(n, alpha, x_dev, beta, y_dev, w_dev, g_scratch.s);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(g_scratch.s));
-    return 0;
-}
-
-int hpccg_hip_HPCCG(HPC_Sparse_Matrix* A, double* b, double* x, int max_iter, double tolerance, int* niters,
-                    double* normr, double* times)
-{
-    if (!A || !b || !x || !niters || !normr) return set_err(HPCCG_HIP_EINVAL, "NULL argument");
-    if (A->local_ncol != A->local_nrow)
-        return set_err(HPCCG_HIP_EPLAN,
-                       "A has local_ncol %d != local_nrow %d: it has been through make_local_matrix (local column "
-                       "indices); pass the matrix with global column indices",
-                       A->local_ncol, A->local_nrow);
-    // A cached image is solved on at once, while host threads fingerprint A
-    // (~23 ms at 200^3, 12 % of the solve); x is written back only if the
-    // fingerprint still matches -- otherwise A changed since it was cached, and
-    // the image is rebuilt and the solve run again from the caller's x.
-    hpccg_hip_matrix* M = nullptr;
-    unsigned long long cached_fp = 0;
-    {
-        std::lock_guard<std::mutex> lk(g_dropin_mu);
-        auto it = g_dropin_cache.find(A);
-        // (the sizes first: the speculative solve reads nrow values of b and x)
-        if (it != g_dropin_cache.end() && it->second.M->nrow == A->local_nrow &&
-            it->second.M->start_row == A->start_row && it->second.M->total_nrow == A->total_nrow)
-            M = it->second.M, cached_fp = it->second.fp;
-    }
-    if (M) {
-        unsigned long long fp = 0;
-        std::thread fth;
-        try {
-            fth = std::thread([&] { fp = fingerprint(A); });
-        } catch (const std::system_error&) {  // no thread to spare: fingerprint first
-            fp = fingerprint(A);
-        }
-        const int rc = solve_host(M, b, x, max_iter, tolerance, niters, normr, times, 0);
-        if (fth.joinable()) fth.join();
-        if (fp == cached_fp) {
-            TRY(rc);
-            print_trace(M, *niters, max_iter);
-            return download_x(M, x);
-        }
-        (void)hipGetLastError();
-        g_err.clear();
-    }
-    double setup = 0.0;
-    {
-        std::lock_guard<std::mutex> lk(g_dropin_mu);
-        const auto t0 = std::chrono::steady_clock::now();
-        const unsigned long long fp = fingerprint(A);
-        auto it = g_dropin_cache.find(A);
-        if (it != g_dropin_cache.end() && it->second.fp == fp) {
-            M = it->second.M;
-        } else {
-            if (it != g_dropin_cache.end()) {  // same address, other contents: a new matrix
-                free_matrix(it->second.M);
-                g_dropin_cache.erase(it);
-            }
-            TRY(hpccg_hip_matrix_create(A, &M));
-            g_dropin_cache[A] = DropinEntry{fp, M};
-        }
-        setup = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    }
-    TRY(hpccg_hip_solve(M, b, x, max_iter, tolerance, niters, normr, times, 1));
-    if (times) times[6] += setup;
-    return 0;
-}
-
-int hpccg_hip_dropin_release(const HPC_Sparse_Matrix* A)
-{
-    std::lock_guard<std::mutex> lk(g_dropin_mu);
-    auto it = g_dropin_cache.find(A);
-    if (it == g_dropin_cache.end()) return 0;
-    free_matrix(it->second.M);
-    g_dropin_cache.erase(it);
-    return 1;
-}
-
-int hpccg_hip_dropin_cached(const HPC_Sparse_Matrix* A)
-{
-    std::lock_guard<std::mutex> lk(g_dropin_mu);
-    return g_dropin_cache.count(A) ? 1 : 0;
-}
-
-long long hpccg_sell_build(int nrow, long long col_base, long long ncol_ext, const long long* row_ptr, const int* cols,
-                           const double* vals, unsigned int* slice_base, int* sell_cols, double* sell_vals)
-{
-    auto row_len = [row_ptr](int i) { return (int)(row_ptr[i + 1] - row_ptr[i]); };
-    auto row_at = [row_ptr, cols, vals](int i, int j, long long* c, double* v) {
-        *c = cols[row_ptr[i] + j];
-        *v = vals ? vals[row_ptr[i] + j] : 0.0;
-    };
-    std::vector<unsigned int> tmp;
-    if (!slice_base) {
-        tmp.resize((nrow + kSliceRows - 1) / kSliceRows + 1);
-        slice_base = tmp.data();
-    }
-    const long long var =
-        sell_build_impl(nrow, SlabCols{col_base, ncol_ext}, row_len, row_at, slice_base, nullptr, nullptr, 0, nullptr);
-    const long long uni =
-        sell_build_impl(nrow, SlabCols{col_base, ncol_ext}, row_len, row_at, slice_base, nullptr, nullptr, 1, nullptr);
-    const int uniform = (uni <= var + var / 25) ? 1 : 0;
-    int bad = 0;
-    const long long r = sell_build_impl(nrow, SlabCols{col_base, ncol_ext}, row_len, row_at, slice_base, sell_cols,
-                                        sell_vals, uniform, &bad);
-    return bad ? HPCCG_HIP_EPLAN : r;
-}
-
-int hpccg_gather_plan(int nranks, const int* info, int nrow, int start_row, const long long* row_ptr, const int* cols,
-                      int cap, int* ext_global, int* num_external, int* nrecv, int* recv_rank, int* recv_off,
-                      int* recv_cnt)
-{
-    if (nranks < 1 || !info || nrow < 0 || (nrow > 0 && (!row_ptr || !cols)) || !num_external || !nrecv)
-        return set_err(HPCCG_HIP_EINVAL, "bad argument");
-    GatherPlan g;
-    gather_externals(
-        nrow, start_row, info, nranks, [row_ptr](int i) { return (int)(row_ptr[i + 1] - row_ptr[i]); },
-        [row_ptr, cols](int i, int j, long long* c, double* v) {
-            *c = cols[row_ptr[i] + j];
-            *v = 0.0;
-        },
-        g);
-    *num_external = (int)g.ext_global.size();
-    *nrecv = (int)g.recv_rank.size();
-    if (ext_global && cap >= *num_external)
-        for (int j = 0; j < *num_external; j++) ext_global[j] = (int)g.ext_global[j];
-    if (recv_rank && recv_off && recv_cnt && cap >= *nrecv)
-        for (int i = 0; i < *nrecv; i++) {
-            recv_rank[i] = g.recv_rank[i];
-            recv_off[i] = g.recv_off[i];
-            recv_cnt[i] = g.recv_cnt[i];
-        }
-    return 0;
-}
-
-int hpccg_slab_plan(int nranks, int rank, const int* info, int sends[2])
-{
-    if (nranks < 1 || rank < 0 || rank >= nranks || !info || !sends) return set_err(HPCCG_HIP_EINVAL, "bad argument");
-    const int r = rank, P = nranks;
-    const int* me = info + 4 * r;
-    const int nrow = me[0], ghost_lo = me[1], ghost_hi = me[2], start_row = me[3];
-    // ghosts must come from the adjacent ranks only, contiguously
-    if (ghost_lo > 0 && (r == 0 || ghost_lo > info[4 * (r - 1)]))
-        return set_err(HPCCG_HIP_EPLAN, "rank %d: ghost_lo %d not owned by rank %d", r, ghost_lo, r - 1);
-    if (ghost_hi > 0 && (r == P - 1 || ghost_hi > info[4 * (r + 1)]))
-        return set_err(HPCCG_HIP_EPLAN, "rank %d: ghost_hi %d not owned by rank %d", r, ghost_hi, r + 1);
-    if (r > 0 && info[4 * (r - 1) + 3] + info[4 * (r - 1)] != start_row)
-        return set_err(HPCCG_HIP_EPLAN, "rank %d: row ranges are not contiguous", r);
-    sends[0] = (r > 0) ? info[4 * (r - 1) + 2] : 0;      // rank-1's ghost_hi: our first rows
-    sends[1] = (r < P - 1) ? info[4 * (r + 1) + 1] : 0;  // rank+1's ghost_lo: our last rows
-    if (sends[0] > nrow || sends[1] > nrow) return set_err(HPCCG_HIP_EPLAN, "rank %d: neighbour needs more rows than owned", r);
-    return 0;
-}
-
-int hpccg_halo_plan(int nrow, int start_row, int total_nrow, const long long* row_ptr, const int* cols, int plan_out[4])
-{
-    long long mn = start_row, mx = (long long)start_row + nrow - 1;
-    for (long long e = 0; e < (nrow > 0 ? row_ptr[nrow] : 0); e++) {
-        mn = std::min<long long>(mn, cols[e]);
-        mx = std::max<long long>(mx, cols[e]);
-    }
-    if (mn < 0 || mx >= total_nrow) return set_err(HPCCG_HIP_EPLAN, "column outside [0, total_nrow)");
-    plan_out[0] = (int)(start_row - mn);
-    plan_out[1] = (int)(mx - ((long long)start_row + nrow - 1));
-    plan_out[2] = (int)mn;
-    plan_out[3] = (int)mx;
     return 0;
 }
 

@@ -28,6 +28,19 @@ def test_library_exports_every_declared_symbol(hp):
     assert "_Z5HPCCGP24HPC_Sparse_Matrix_STRUCTPdS1_idRiRdS1_" in out
 
 
+def test_library_exports_exactly_the_pinned_symbols(hp):
+    """The dynamic symbol table of libhpccg_hip.so is tests/golden/libhpccg_hip_exports.txt:
+    the defined T, D, B and R names, sorted, without the compiler's __hip_cuid_* marker.
+    Weak symbols (W, V, u: the standard library's template instantiations) are left out."""
+    out = subprocess.run(["nm", "-D", "--defined-only", hp.LIB_PATH], capture_output=True,
+                         text=True, check=True).stdout
+    built = sorted(f[2] for f in (line.split() for line in out.splitlines())
+                   if len(f) == 3 and f[1] in "TDBR" and not f[2].startswith("__hip_cuid_"))
+    with open(os.path.join(ROOT, "tests", "golden", "libhpccg_hip_exports.txt")) as f:
+        pinned = f.read().split()
+    assert built == pinned, sorted(set(built) ^ set(pinned))
+
+
 def test_cli_built_and_usage(hp):
     assert os.path.exists(hp.CLI_PATH)
     r = subprocess.run([hp.CLI_PATH], capture_output=True, text=True)

@@ -255,6 +255,25 @@ def srcg_lib() -> C.CDLL:
     })
 
 
+BICGSTAB_LIB_PATH = os.path.join(HERE, "lib", "bicgstab", "libhpccg_hip_bicgstab.so")
+
+
+def bicgstab_lib() -> C.CDLL:
+    """Load lib/bicgstab/libhpccg_hip_bicgstab.so (include/hpccg_hip_bicgstab.h)
+    on first use. It is linked against libhpccg_hip.so one directory up, so
+    lib() is loaded first and both share one copy of the main library."""
+    return _load_unit("bicgstab", BICGSTAB_LIB_PATH, "the bicgstab library", "the BiCGStab solve has no fallback", {
+        "hpccg_hip_bicgstab_abi_version": (_ip, []),
+        "hpccg_hip_bicgstab_solve_device": (_ip, [_vp, _ip, _vp, _lp, _vp, _lp, _vp, _ip, _dp, _PI, _PD, _PD]),
+        "hpccg_hip_bicgstab_solve": (_ip, [_vp, _ip, _vp, _lp, _vp, _lp, _vp, _ip, _dp, _PI, _PD, _PD]),
+        "hpccg_hip_bicgstab_last_trace": (_ip, [_vp, _ip, _PD, _ip]),
+        "hpccg_hip_bicgstab_last_status": (_ip, [_vp, _ip, _PI]),
+        "hpccg_hip_bicgstab_release": (_ip, [_vp]),
+        "hpccg_hip_bicgstab_workspace_bytes": (_ip, [_vp, _PL]),
+        "hpccg_hip_bicgstab_live_workspaces": (_ip, [_PI]),
+    })
+
+
 PCG_GROUP_LIB_PATH = os.path.join(HERE, "lib", "libhpccg_hip_pcg_group.so")
 
 
@@ -459,6 +478,11 @@ def pcg_exported_symbols() -> list[str]:
 def srcg_exported_symbols() -> list[str]:
     """Functions include/hpccg_hip_srcg.h declares (checked by the CPU suite)."""
     return _declared("hpccg_hip_srcg.h", r"\b(hpccg_hip_srcg_\w+)\s*\(")
+
+
+def bicgstab_exported_symbols() -> list[str]:
+    """Functions include/hpccg_hip_bicgstab.h declares (checked by the CPU suite)."""
+    return _declared("hpccg_hip_bicgstab.h", r"\b(hpccg_hip_bicgstab_\w+)\s*\(")
 
 
 def group_srcg_exported_symbols() -> list[str]:
@@ -840,6 +864,29 @@ class Matrix:
     def srcg_workspace_bytes(self) -> int:
         return _workspace_bytes("srcg", "srcg_workspace_bytes", self.h)
 
+    def last_trace_bicgstab(self, col: int, cap: int = 100000) -> np.ndarray:
+        """Residual trace (norm of r) of column col of the last HPCCG_bicgstab on this matrix."""
+        out = np.zeros(cap, np.float64)
+        n = bicgstab_lib().hpccg_hip_bicgstab_last_trace(self.h, int(col), out.ctypes.data_as(C.POINTER(C.c_double)),
+                                                         cap)
+        if n < 0:
+            _check(n, "last_trace_bicgstab")
+        return out[:n]
+
+    def last_status_bicgstab(self, col: int) -> int:
+        """How column col of the last HPCCG_bicgstab on this matrix ended: 0 the
+        loop test, 1 breakdown, 2 an exactly zero residual."""
+        st = C.c_int(-1)
+        _check(bicgstab_lib().hpccg_hip_bicgstab_last_status(self.h, int(col), C.byref(st)), "last_status_bicgstab")
+        return st.value
+
+    def bicgstab_release(self) -> None:
+        """Free this matrix's bicgstab workspace (with its cached 1 / a_ii) now (close() does it too)."""
+        _release("bicgstab", "bicgstab_release", self.h)
+
+    def bicgstab_workspace_bytes(self) -> int:
+        return _workspace_bytes("bicgstab", "bicgstab_workspace_bytes", self.h)
+
     def last_trace_poly(self, col: int, cap: int = 100000) -> np.ndarray:
         """Residual trace (norm of r) of column col of the last HPCCG_poly on this matrix."""
         out = np.zeros(cap, np.float64)
@@ -1151,6 +1198,26 @@ def HPCCG_srcg(M: Matrix, B, X, max_iter: int = 500, tolerance: float = 0.0, min
 def srcg_live_workspaces() -> int:
     """Matrices that hold a srcg workspace (0 when the library was never loaded)."""
     return _live("srcg", "srcg_live_workspaces")
+
+
+# ---------------------------------------------------------------------------
+# BiCGStab for non-symmetric matrices (include/hpccg_hip_bicgstab.h)
+# ---------------------------------------------------------------------------
+def HPCCG_bicgstab(M: Matrix, B, X, max_iter: int = 500, tolerance: float = 0.0, minv=None, device=False, nrhs=None,
+                   ldb=None, ldx=None):
+    """nrhs right-preconditioned BiCGStab solves against M, symmetric or not,
+    with M^-1 = diag(minv) (hpccg_hip_bicgstab_solve[_device]); minv None is
+    Jacobi, 1 / a_ii. The loop test, niters and normr are on the 2-norm of r,
+    as in HPCCG; how a column ended is M.last_status_bicgstab(c). B, X, minv
+    and the return value: as HPCCG_pcg. X is updated in place."""
+    L = bicgstab_lib()
+    return _column_solve("HPCCG_bicgstab", L.hpccg_hip_bicgstab_solve_device if device else L.hpccg_hip_bicgstab_solve,
+                         M, B, X, minv, device, nrhs, ldb, ldx, max_iter, tolerance)
+
+
+def bicgstab_live_workspaces() -> int:
+    """Matrices that hold a bicgstab workspace (0 when the library was never loaded)."""
+    return _live("bicgstab", "bicgstab_live_workspaces")
 
 
 # ---------------------------------------------------------------------------
